@@ -4,10 +4,13 @@
 Workload (BASELINE.json configs[2], "C3"): 2^20 x 1500 B synthetic Eth/IPv4/TCP frames per
 GPU, 1 000 flows + 1 listener, 8-byte records (--rec 16 for the other kind), two rotating
 1.5 GiB batches, inputs resident in HBM before timing.  One step = one rxg_rx_burst_dev over the
-whole batch.  Legs beside it: C2 64 B frames with a rotating 1 GiB working set
-(16 copies of 2^20 frames) so the 256 MiB Infinity Cache cannot hold it, C4 IMIX, the fused
-payload hand-off, tx generate, copy-inclusive C3 / C5, burst + replay under churn, small-burst
-latency; the CPU baseline at N = 1.
+whole batch.  A plain run sets up, warms up, times --steps steps and prints the line;
+--dump-outputs DIR also writes the last timed step's records (and the region's counters) as
+DIR/<name>.npy (dump_outputs).  --full adds everything measured beside the headline: the
+per-launch event-pair pass, the legs: C2 64 B frames with a rotating 1 GiB
+working set (16 copies of 2^20 frames) so the 256 MiB Infinity Cache cannot hold it, C4 IMIX,
+the fused payload hand-off, tx generate, copy-inclusive C3 / C5, burst + replay under churn,
+small-burst latency; and the CPU baseline at N = 1.
 
 Multi-GPU: one process per GPU (torch.distributed.run), weak scaling, every rank its own
 shard (seed + rank) and a replica of the TCB mirror; no data-path collective.  The only
@@ -225,6 +228,39 @@ def time_region(eng, wl, steps, warmup, device, stream, strided=False):
     eng.event_destroy(e0)
     eng.event_destroy(e1)
     return elapsed, region_ms
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all of --dump-outputs' files together stay below 64 MB
+
+
+def dump_rows(n: int, words: int, budget: int = None):
+    """The records --dump-outputs writes of an n-record output: None for all of them when
+    they fit the budget (8 bytes per word, float64), else a fixed sample of row numbers
+    (seeded, ascending, the same from run to run; each row then costs its number too)."""
+    budget = DUMP_BUDGET_BYTES if budget is None else budget
+    if n * words * 8 <= budget:
+        return None
+    keep = budget // ((words + 1) * 8)
+    return np.sort(np.random.default_rng(0x5EED0001).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(dirname: str, records: np.ndarray, counters: np.ndarray) -> dict:
+    """--dump-outputs DIR: what the timed path handed its caller, for an output-for-output
+    comparison of two builds on the same arguments (the inputs are generated from fixed seeds).
+      records.npy       float64 [rows, record bytes / 4]: the records rxg_rx_burst_dev wrote in
+                        the LAST timed step, as their little-endian 32-bit words (exact in float64)
+      records_rows.npy  float64 [rows]: which records those are, only when the whole output
+                        exceeds the budget (dump_rows)
+      counters.npy      float64 [16]: this rank's counters over the timed region (rxg.COUNTERS)"""
+    os.makedirs(dirname, exist_ok=True)
+    words = records.view(np.uint8).reshape(len(records), -1).view("<u4")
+    rows = dump_rows(*words.shape)
+    if rows is not None:
+        words = words[rows]
+        np.save(os.path.join(dirname, "records_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "records.npy"), words.astype(np.float64))
+    np.save(os.path.join(dirname, "counters.npy"), np.asarray(counters).astype(np.float64))
+    return {"dir": dirname, "records": list(words.shape), "sampled": rows is not None}
 
 
 def multiburst_leg(eng, steps, warmup, device, seed, nbursts=16, n=1 << 20, rec=rxg.REC16, strided=False):
@@ -520,6 +556,7 @@ def tx_leg(eng, wl, steps, warmup):
 # next barrier: together they may take at most this long (subprocess time limits), far below
 # --pg-timeout, so no waiting rank's collective can time out on them.
 SOLO_BUDGET_S = 180.0
+COPY_LEG_MAX_STEPS = 200  # the copy-inclusive legs' steps (unchanged below --steps 800)
 
 
 def replay_churn_leg(deadline=None):
@@ -832,8 +869,14 @@ def main():
     # record kind: 8 = rxg_rec8, everything rxg_rx_replay and the payload gather read
     # (checksums as ok bits); 16 / 48 carry the checksum values / every header field
     ap.add_argument("--rec", type=int, default=8, choices=[8, 16, 48])
-    ap.add_argument("--no-legs", action="store_true", help="skip the 64 B / IMIX legs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-launch event-pair pass, "
+                         "the legs and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records and the timed region's counters as "
+                         "DIR/<name>.npy (rank 0's shard; dump_outputs)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the 64 B / IMIX legs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="replicas for the multi-core CPU leg (0: this process's CPU share, at most 16)")
@@ -849,6 +892,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit(f"bench.py: --gpus {args.gpus}: need at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"bench.py: --steps {args.steps} --warmup {args.warmup}: need at least 1 timed step")
 
     # RXG_BENCH_REHEARSE=1: rehearse N ranks on fewer GPUs (device = local_rank mod #GPUs,
     # gloo backend for the collectives) -- a correctness rehearsal, never a measurement.
@@ -905,10 +950,13 @@ def main():
 
     elapsed, region_ms = time_region(eng, wl, args.steps, args.warmup, device, stream)
     cnt = eng.counters()
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else writes wl.out again
+        dumped = dump_outputs(args.dump_outputs, wl.out.download(rxg.rec_dtype(args.rec), wl.n), cnt)
     elapsed_max = max_over_ranks(elapsed, device)
     merged = merge_counters(cnt, device)
     # per-launch event pairs, a separate pass after the timed region (distribution only)
-    _, kern_ms = time_workload(eng, wl, args.steps, 2, device, stream)
+    kern_ms = time_workload(eng, wl, args.steps, 2, device, stream)[1] if args.full else None
 
     total_frames = int(sum_over_ranks(wl.n, device)) * args.steps
     total_bytes = int(sum_over_ranks(wl.bytes_per_batch, device)) * args.steps
@@ -916,7 +964,7 @@ def main():
     mpps = total_frames / elapsed_max / 1e6
     # the kernel's average launch duration: the timed region's event time / launches
     k_avg_s = region_ms / args.steps / 1e3
-    k_med_s = float(np.median(kern_ms)) / 1e3
+    k_med_s = float(np.median(kern_ms)) / 1e3 if kern_ms else None
     # every rank's mean kernel time; the roofline is quoted on the slowest GPU
     k_max_s = max_over_ranks(k_avg_s, device)
     k_min_s = min_over_ranks(k_avg_s, device)
@@ -927,7 +975,7 @@ def main():
                  and C["dispatch"] == total_frames and C["tcb_hit_exact"] == total_frames)
 
     legs = {}
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         # the headline workload with the other record kind (16 <-> 8 bytes), right after the
         # headline timing so that both see the same clocks
         other = rxg.REC16 if args.rec == rxg.REC8 else rxg.REC8
@@ -980,9 +1028,11 @@ def main():
         legs["c3_rx_payload_fused"]["two_pass_us"] = round(two, 2)  # rx_burst_dev + payload_gather_dev
         legs["c3_rx_payload_by_reference"] = fused_leg(eng, wl, args.steps, 2, by_reference=True)
         legs["tx_generate_dev"] = tx_leg(eng, wl, args.steps, 2)
-        legs["c3_copy_inclusive"] = copy_inclusive_leg(eng, wl, max(3, args.steps // 4), 1, device)
-        legs["c5_bidir_copy_inclusive"] = c5_leg(eng, frames, max(3, args.steps // 4), 1, device,
-                                                 seed)
+        # PCIe-bound, 16-29 ms per step: a quarter of --steps, at most COPY_LEG_MAX_STEPS, so that
+        # a --full run with a large --steps still ends in minutes
+        copy_steps = min(max(3, args.steps // 4), COPY_LEG_MAX_STEPS)
+        legs["c3_copy_inclusive"] = copy_inclusive_leg(eng, wl, copy_steps, 1, device)
+        legs["c5_bidir_copy_inclusive"] = c5_leg(eng, frames, copy_steps, 1, device, seed)
         if rank == 0:  # bounded: SOLO_BUDGET_S (the others wait at the barrier below)
             deadline = time.perf_counter() + min(SOLO_BUDGET_S, args.pg_timeout / 3)
             legs["replay_churn"] = replay_churn_leg(deadline)
@@ -993,7 +1043,7 @@ def main():
     # independent of N, timed by rank 0 after the timed region of the N = 1 run only (the
     # driver's N > 1 lines carry null; the other ranks would only wait at the barrier).
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cores = args.cpu_cores or host_cpus()["usable"]
         cpu = cpu_baseline(eng, wl, seconds=args.cpu_seconds, cores=cores)
     barrier(device)
@@ -1018,6 +1068,8 @@ def main():
             "collective_backend": dist.get_backend() if dist.is_initialized() else None,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
+            "dumped_outputs": dumped,
             "ms_per_step": round(elapsed_max / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -1042,7 +1094,8 @@ def main():
                          "traffic_matches_build": tprov["traffic_matches_build"],
                          "leg_traffic_files": len(leg_files), "leg_traffic_files_stale": stale,
                          "kernel_us": round(k_max_s * 1e6, 2),
-                         "kernel_us_per_launch_pairs_rank0_median": round(k_med_s * 1e6, 2),
+                         "kernel_us_per_launch_pairs_rank0_median":
+                             round(k_med_s * 1e6, 2) if k_med_s is not None else None,  # --full
                          "kernel_us_min_over_ranks": round(k_min_s * 1e6, 2),
                          "kernel_us_max_over_ranks": round(k_max_s * 1e6, 2),
                          "kernel_timing": "one HIP event pair on the launch stream around the timed "

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The round's evidence on the shipped tree, in one GPU call: the GPU suite, smoke, rocprofv3 of
 # the bench command, the stamped PMC passes of every leg the bench line cites (REC 8 and 16), and
-# the default bench line.  Outputs under gpurun_out/$TAG/; scripts/collect_profiles.sh copies
+# the full bench line (bench.py --full).  Outputs under gpu_check.sh's folder for $TAG; scripts/collect_profiles.sh copies
 # them into profiles/.  Stops at the first failing step (gpu_check.sh).
 #   bash scripts/gpu_final.sh r06
 set -eu

@@ -80,6 +80,56 @@ def test_pg_backend_choice():
     assert bench.SOLO_BUDGET_S < 900.0 / 3  # the solo legs end well inside the default timeout
 
 
+def test_steps_must_be_at_least_one():
+    r = _run(["--gpus", "1", "--steps", "0"], {"RXG_BENCH_REHEARSE": "1"})
+    assert r.returncode != 0 and "--steps 0" in r.stderr
+
+
+def test_dump_outputs_writes_exact_words(tmp_path):
+    """--dump-outputs: the records as their 32-bit words in float64 (exact at every bit), the
+    counters beside them, and no row list while the whole output fits the budget."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import rxg
+    n = 1000
+    for dt in (rxg.REC8_DTYPE, rxg.REC16_DTYPE, rxg.REC48_DTYPE):
+        raw = np.random.default_rng(5).integers(0, 1 << 32, size=(n, dt.itemsize // 4), dtype=np.uint64)
+        raw[0, :] = 0xFFFFFFFF
+        rec = raw.astype("<u4").view(dt).reshape(n)
+        out = tmp_path / f"rec{dt.itemsize}"
+        d = bench.dump_outputs(str(out), rec, np.arange(16, dtype=np.uint64) << 40)
+        got = np.load(out / "records.npy")
+        assert got.dtype == np.float64 and got.shape == (n, dt.itemsize // 4) and d["records"] == list(got.shape)
+        assert np.array_equal(got.astype(np.uint64), raw) and not d["sampled"]
+        assert not (out / "records_rows.npy").exists()
+        cnt = np.load(out / "counters.npy")
+        assert cnt.dtype == np.float64 and np.array_equal(cnt.astype(np.uint64), np.arange(16, dtype=np.uint64) << 40)
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """An output beyond the budget is written as a fixed sample: the same ascending rows every
+    time, named in records_rows.npy, every file together inside the budget; the default budget
+    keeps the headline's 2^20 records whole and samples 2^23 48-byte ones below 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import rxg
+    assert bench.dump_rows(1 << 20, 2) is None
+    big = bench.dump_rows(1 << 23, 12)
+    assert len(big) * 13 * 8 <= bench.DUMP_BUDGET_BYTES < 64 * 10**6 - 16 * 8 - 3 * 128
+    n = 5000
+    rec = np.zeros(n, dtype=rxg.REC8_DTYPE)
+    rec["w0"], rec["w1"] = np.arange(n), 0xFFFFFFFF - np.arange(n)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2400)
+    d = bench.dump_outputs(str(tmp_path), rec, np.zeros(16, dtype=np.uint64))
+    rows, got = np.load(tmp_path / "records_rows.npy"), np.load(tmp_path / "records.npy")
+    assert d["sampled"] and rows.dtype == np.float64 and len(rows) == 100 and got.shape == (100, 2)
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(got[:, 0], rows) and np.array_equal(got[:, 1], 0xFFFFFFFF - rows)
+    assert np.array_equal(rows, bench.dump_rows(n, 2).astype(np.float64))  # the same rows again
+
+
 def test_traffic_provenance_reports_a_mismatched_build(tmp_path):
     """roofline.traffic names the build its PMC passes counted
     (scripts/pmc_traffic.py --prov stamps the src= hash), and the line says whether that is
