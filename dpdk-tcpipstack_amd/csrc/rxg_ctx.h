@@ -1,7 +1,9 @@
 // rxg_ctx.h — the context behind the rxg C ABI (include/rxg.h), shared by the host-side
 // translation units (internal: not installed, not part of the ABI):
-//   rxg_host.cpp    context, TCB / ARP mirrors, table-reader ordering, launched bursts, tx,
-//                   counters
+//   rxg_host.cpp    context, TCB / ARP mirrors, launched bursts, tx, counters, and
+//                   HipTablePort, the device side of rxg_tablesync.h
+//   rxg_tablesync.h the device tables and the order of their writes against the kernels that
+//                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
 //   rxg_replay.cpp  the per-packet replay into the caller's handlers, the payload hand-off,
 //                   ether_in
@@ -24,6 +26,7 @@
 #include "rxg_opqueue.h"
 #include "rxg_packpool.h"
 #include "rxg_srvfsm.h"
+#include "rxg_tablesync.h"
 
 // Everything below is internal to librxg.so: hidden, never exported.
 #pragma GCC visibility push(hidden)
@@ -39,10 +42,7 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
                         __LINE__);                                                          \
     } while (0)
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
+using rxg::DevBuf;
 
 // The latency-mode server's device side as rxg::SrvFsm sees it (rxg_srvfsm.h); defined in
 // rxg_server.cpp.
@@ -57,13 +57,35 @@ struct SrvPort {
     void sync();
 };
 
+// The device side of the table synchronisation as rxg::TableSync sees it (rxg_tablesync.h:
+// the Port's contract); defined in rxg_host.cpp, the only HIP calls on those paths.
+struct HipTablePort {
+    using Stream = hipStream_t;
+    using Event = hipEvent_t;
+    rxg_ctx *c = nullptr;
+    Stream stream() const;
+    int event_create(Event *e, bool reader);
+    void event_destroy(Event e);
+    int record(Event e, Stream s);
+    int stream_wait(Stream s, Event e);
+    int host_wait(Event e);
+    int sync();
+    int patch_alloc(rxg::MirrorPatch **p, uint32_t cap, bool dev);
+    int patch_free(rxg::MirrorPatch *p, bool dev);
+    void patch_write(rxg::MirrorPatch *dst, const rxg::MirrorPatch *src, uint32_t n, bool dev);
+    int patch_launch(const rxg::MirrorPatch *list, uint32_t n, const DevBuf &buckets, const DevBuf &listen,
+                     const DevBuf &arp);
+    int table_resize(DevBuf &b, size_t bytes);
+    int table_upload(DevBuf &b, const void *src, size_t bytes);
+};
+
 struct rxg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t max_blocks = 0;        // rxg_config.max_blocks: grid cap (0 = occupancy grid)
     uint32_t grid_pay = 512;        // rxg_rx_burst_payload_dev's grid (set at init)
-    uint32_t grid_rec8 = 0, grid_rec16 = 0, grid_rec48 = 0, grid_tx = 0;
-    uint32_t grid_ref8 = 0, grid_ref16 = 0, grid_ref48 = 0;  // the by-reference hand-off's
+    // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
+    uint32_t grid[2][4] = {};
     rxg::PackPool pack_pool;  // rxg_rx_burst's packing threads
 
     // tcbs[] writes posted by other threads (rxg_tcb_post), applied by the rx thread
@@ -71,56 +93,9 @@ struct rxg_ctx {
 
     // host mirror of tcbs[0..ntcb) and the device words each write changes (rxg_mirror.h)
     rxg::TcbMirror mir;
-    bool dirty = true;  // mirror writes not on the device yet
 
-    // device mirror
-    DevBuf buckets, listen;
-    uint32_t bucket_mask = 0;
-    int32_t dev_ntcb = 0;
-    int32_t dev_min_null = INT32_MAX;
-    // Ordering of table writes against the kernels that read the tables:
-    // mirror writes run on `stream`; a burst on another stream waits for mirror_ev (once per
-    // write), and the next mirror write waits for every stream other than `stream` that
-    // launched a table-reading kernel since the last write (one entry per stream, so a
-    // reader on s1 followed by one on s2 are both waited for): the event recorded after the
-    // stream's latest such launch, or, with RXG_CFG_STREAMS_OUTLIVE_WRITES, recorded on the
-    // stream at the write, which keeps the caller's stream free of a marker packet per launch
-    // (C4 on a caller stream 78.2 -> 73.2 us per launch, C2 24.5 -> 20.3).
-    hipEvent_t mirror_ev = nullptr;
-    bool mirror_ev_set = false;
-    bool mirror_ev_stale = false;  // a write on `stream` after mirror_ev's last recording
-                                   // (recorded when another stream or the server needs it)
-    uint64_t table_writes = 0;  // mirror_ev recordings (device table writes) so far
-    struct Reader {
-        hipStream_t s;
-        hipEvent_t e;
-        bool pending;     // `s` launched a table reader since the last write (not yet waited for)
-        bool recorded;    // e was recorded after that launch (per-launch mode)
-        uint64_t waited;  // table_writes when `s` last waited for mirror_ev (~0: never)
-    };
-    std::vector<Reader> readers;
-    // Patch upload ring: a list is read by its patch kernel or by the burst that carries it
-    // (device memory the host writes through a large BAR, else pinned host memory read over
-    // PCIe), so a buffer is reused only after that launch ran; kPatchBufs buffers, each with
-    // its event, and the host waits only when all of them are in flight (a patch kernel waits
-    // on the device for bursts running on caller streams, which can be long).
-    static constexpr int kPatchBufs = 4;
-    struct PatchBuf {
-        rxg::MirrorPatch *h = nullptr;
-        uint32_t cap = 0;
-        hipEvent_t ev = nullptr;
-        bool set = false;
-    } patch[kPatchBufs];
-    int patch_next = 0;
-    // With a large BAR the patch buffers are device memory the host writes through the BAR,
-    // and a launch on `stream` carries the burst's patch list itself (launch_bursts: no patch
-    // launch before it); defer_patch asks apply_patches for that, ip_* is the list taken.
-    bool patch_dev = false;
-    bool defer_patch = false;
-    const rxg::MirrorPatch *ip_list = nullptr;
-    uint32_t ip_n = 0;
-    int ip_buf = -1;
-    uint32_t ip_tables = 0;  // 1 << target of every patch in the carried list (rxg_mirror.h)
+    // the device tables and the order of their writes against their readers (rxg_tablesync.h)
+    rxg::TableSync<HipTablePort> tables;
     // HDP_MEM_COHERENCY_FLUSH_CNTL (hipDeviceProp_t::hdpMemFlushCntl; null if the runtime
     // gives none): host writes through the BAR are flushed to memory before a kernel reads them
     volatile uint32_t *hdp_flush = nullptr;
@@ -138,8 +113,6 @@ struct rxg_ctx {
     bool touched_all = false;            // whole table replaced
     bool touched_pass2 = false;          // min_null moved (the pass-2 NULL-slot flag)
     bool replay_on_device = false;       // RXG_CFG_REPLAY_ON_DEVICE
-    bool lazy_readers = false;           // RXG_CFG_STREAMS_OUTLIVE_WRITES
-    std::vector<hipStream_t> registered; // that mode's caller streams (rxg_stream_register)
     uint64_t rp_stats[4] = {0, 0, 0, 0}; // marked, host fix-ups, device fix-ups, launches
 
     // the last burst's device batch (re-classification reads it again)
@@ -187,11 +160,9 @@ struct rxg_ctx {
     int64_t replay_pos = -1;  // packet whose handlers rxg_rx_replay is running
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
-    bool arp_enabled = false, arp_dirty = false;
+    bool arp_enabled = false;
     rxg::ArpMirror arp;
     std::unordered_map<uint32_t, int> arp_since_burst;  // learned after the last burst
-    DevBuf d_arp;
-    uint32_t arp_mask = 0;
 
     // replay scratch, kept across calls
     std::vector<rxg_rec16> rp_cur;
@@ -238,13 +209,9 @@ struct rxg_ctx {
         uint32_t rec_kind = 0, blocks = 1, max_frames = 0;
         uint64_t max_bytes = 0, idle_ticks = 0;
         unsigned long long seq = 0;
-        uint64_t synced_writes = 0;    // table_writes whose mirror_ev the host has waited for
+        uint64_t synced_writes = 0;    // table writes the host has waited for (host_wait_writes)
     } srv;
 };
-
-// patch lists longer than this go through their own launch (every workgroup of a launch that
-// carries a list stores all of it)
-inline constexpr uint32_t kLaunchPatchMax = 256;
 
 // Host stores into device memory through the BAR (write-combined), made visible to the next
 // kernel: the CPU's write-combining buffers drained (sfence), the GPU's HDP write path flushed
@@ -278,26 +245,33 @@ inline hipStream_t pick(rxg_ctx *c, void *s) { return s ? (hipStream_t)s : c->st
 // The device tables as the kernels read them (DevTable, rxg_kernels.h).
 inline rxg::DevTable table_view(const rxg_ctx *c)
 {
-    rxg::DevTable t;
-    t.buckets = (const uint4 *)c->buckets.p;
-    t.listen = (const int32_t *)c->listen.p;
-    t.bucket_mask = c->bucket_mask;
-    t.ntcb = c->dev_ntcb;
-    t.min_null = c->dev_min_null;
-    t.arp = (const uint4 *)c->d_arp.p;
-    t.arp_mask = c->arp_enabled ? c->arp_mask : 0u;
+    rxg::DevTable t = c->tables.view();
+    if (!c->arp_enabled) t.arp_mask = 0u;
     t.arp_flags = c->arp_enabled ? (rxg::kArpOn | (c->arp.has_zero ? rxg::kArpZero : 0u)) : 0u;
     return t;
 }
 
+inline hipStream_t HipTablePort::stream() const { return c->stream; }
+
+// A launch's grid: the max_blocks override, else the occupancy grid of the kernel for
+// rec_kind (0: tx) and whether it is the by-reference hand-off's.
+inline int grid_slot(uint32_t rec_kind)
+{
+    return rec_kind == RXG_REC8 ? 1 : rec_kind == RXG_REC16 ? 2 : rec_kind == RXG_REC48 ? 3 : 0;
+}
+inline uint32_t grid_for(const rxg_ctx *c, uint32_t rec_kind, bool by_ref = false)
+{
+    const uint32_t g = c->max_blocks ? c->max_blocks : c->grid[by_ref][grid_slot(rec_kind)];
+    return g ? g : 1024;
+}
+
 // rxg_host.cpp: the mirror upload, the replay bookkeeping of a burst set and its offsets.
+// tcb_push: the device TCB tables brought up to date with the mirror (nothing if they are).
 int tcb_push(rxg_ctx *c);
 void select_burst(rxg_ctx *c, uint32_t j);
 int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, uint32_t k, uint32_t rec_kind,
-                 const char *who, uint32_t stride64 = 0);
+                 const char *who, uint32_t stride64 = 0, bool carry = false);
 int burst_offsets(rxg_ctx *c, hipStream_t st, const uint32_t **out);
-// mirror_ev recorded on `stream` if a write since its last recording has not been (rxg_host.cpp)
-int mirror_event(rxg_ctx *c);
 // the pending counter corrections (rxg_ctx::pend_delta) to the device, on c->stream
 int flush_delta(rxg_ctx *c);
 

@@ -75,13 +75,10 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
     if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) {
         // one generation of resident workgroups per CU (grid-stride over slices)
         const uint32_t cus = (uint32_t)prop.multiProcessorCount;
-        c->grid_rec8 = cus * (uint32_t)rx_blocks_per_cu(8);
-        c->grid_rec16 = cus * (uint32_t)rx_blocks_per_cu(16);
-        c->grid_rec48 = cus * (uint32_t)rx_blocks_per_cu(48);
-        c->grid_tx = cus * (uint32_t)rx_blocks_per_cu(0);
-        c->grid_ref8 = cus * (uint32_t)rx_blocks_per_cu(8, true);
-        c->grid_ref16 = cus * (uint32_t)rx_blocks_per_cu(16, true);
-        c->grid_ref48 = cus * (uint32_t)rx_blocks_per_cu(48, true);
+        for (int kind : {0, (int)RXG_REC8, (int)RXG_REC16, (int)RXG_REC48}) {  // 0: tx
+            c->grid[0][grid_slot(kind)] = cus * (uint32_t)rx_blocks_per_cu(kind);
+            if (kind) c->grid[1][grid_slot(kind)] = cus * (uint32_t)rx_blocks_per_cu(kind, true);
+        }
         // the fused burst + payload hand-off moves as many bytes out as in: 2 workgroups per CU
         // (8 waves) measured faster than the occupancy grid's 3 (C3 621 against 627 us, C4 174
         // against 177)
@@ -90,18 +87,18 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
     int large_bar = 0;
+    bool bar_lists = false;
     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, c->device) == hipSuccess && large_bar) {
         void *probe = nullptr;  // and host-writable device memory can be had
         if (hipExtMallocWithFlags(&probe, 4096, hipDeviceMallocFinegrained) == hipSuccess) {
             (void)hipFree(probe);
-            c->patch_dev = true;
+            bar_lists = true;
         }
         hipDeviceProp_t hp;
         if (hipGetDeviceProperties(&hp, c->device) == hipSuccess) c->hdp_flush = hp.hdpMemFlushCntl;
     }
     if (cfg) {
         c->replay_on_device = (cfg->flags & RXG_CFG_REPLAY_ON_DEVICE) != 0;
-        c->lazy_readers = (cfg->flags & RXG_CFG_STREAMS_OUTLIVE_WRITES) != 0;
         c->max_blocks = cfg->max_blocks;
         if (cfg->zc_bytes) c->zc_bytes = cfg->zc_bytes;
     }
@@ -109,9 +106,8 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         delete c;
         return fail(-EIO, "rxg_init: hipStreamCreate failed");
     }
-    bool ev_ok = hipEventCreateWithFlags(&c->mirror_ev, hipEventDisableTiming) == hipSuccess;
-    for (auto &pb : c->patch) ev_ok = ev_ok && hipEventCreateWithFlags(&pb.ev, hipEventDisableTiming) == hipSuccess;
-    if (!ev_ok) {
+    c->tables.port.c = c;
+    if (c->tables.init(bar_lists, cfg && (cfg->flags & RXG_CFG_STREAMS_OUTLIVE_WRITES) != 0)) {
         rxg_fini(c);
         return fail(-EIO, "rxg_init: hipEventCreate failed");
     }
@@ -122,7 +118,8 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
     }
     // the ARP bucket every lane reads while the mirror is off (classify_finish issues the
     // ARP probe unconditionally)
-    if (ensure(c->d_arp, 256) || hipMemset(c->d_arp.p, 0, c->d_arp.bytes) != hipSuccess) {
+    DevBuf &arp0 = c->tables.d_arp;
+    if (ensure(arp0, 256) || hipMemset(arp0.p, 0, arp0.bytes) != hipSuccess) {
         rxg_fini(c);
         return fail(-ENOMEM, "rxg_init: ARP mirror");
     }
@@ -162,20 +159,13 @@ extern "C" int rxg_fini(rxg_ctx *c)
         return fail(-EIO, "rxg_fini: the server kernel has not exited; the context and every buffer it can "
                           "reach are left allocated (leaked)");
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto &r : c->readers)  // table readers still running on caller streams
-        if (r.pending && (r.recorded || hipEventRecord(r.e, r.s) == hipSuccess))
-            (void)hipEventSynchronize(r.e);
-    for (DevBuf *b : {&c->buckets, &c->listen, &c->d_sel, &c->d_fix, &c->d_arp, &c->d_pg_status, &c->d_pg_ticket,
-                      &c->d_soff})
+    (void)c->tables.wait_readers(true);  // table readers still running on caller streams
+    for (DevBuf *b : {&c->tables.buckets, &c->tables.listen, &c->d_sel, &c->d_fix, &c->tables.d_arp, &c->d_pg_status,
+                      &c->d_pg_ticket, &c->d_soff})
         if (b->p) (void)hipFree(b->p);
     if (c->h_pm) (void)hipHostFree(c->h_pm);
     if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
-    for (auto &pb : c->patch) {
-        if (pb.h) (void)(c->patch_dev ? hipFree(pb.h) : hipHostFree(pb.h));
-        if (pb.ev) (void)hipEventDestroy(pb.ev);
-    }
-    for (auto &r : c->readers) (void)hipEventDestroy(r.e);
-    if (c->mirror_ev) (void)hipEventDestroy(c->mirror_ev);
+    c->tables.destroy();
     if (c->counters) (void)hipFree(c->counters);
     if (c->h_arena) (void)hipHostFree(c->h_arena);
     if (c->h_off) (void)hipHostFree(c->h_off);
@@ -225,7 +215,7 @@ extern "C" int rxg_tcb_upsert(rxg_ctx *c, int32_t idx, const rxg_tcb_tuple *t)
     // NULL slots appearing (old Ntcb .. idx-1) or disappearing (a removed slot reused) move
     // min_null, the pass-2 NULL-slot flag of later packets
     if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched_pass2 = true;
-    c->dirty = true;
+    c->tables.tcb_changed();
     c->gen++;
     return 0;
 }
@@ -240,7 +230,7 @@ extern "C" int rxg_tcb_remove(rxg_ctx *c, int32_t idx)
     c->mir.remove(idx);
     if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched_pass2 = true;
     if ((size_t)idx < c->rcv_state.size()) c->rcv_state[idx] = 0;  // FreeWindow
-    c->dirty = true;
+    c->tables.tcb_changed();
     c->gen++;
     return 0;
 }
@@ -254,7 +244,7 @@ extern "C" int rxg_tcb_set_state(rxg_ctx *c, int32_t idx, uint8_t state)
     note_slot(c, idx);
     c->mir.set_state(idx, state);
     note_slot(c, idx);
-    c->dirty = true;
+    c->tables.tcb_changed();
     c->gen++;
     return 0;
 }
@@ -267,7 +257,7 @@ extern "C" int rxg_tcb_load(rxg_ctx *c, const rxg_tcb_tuple *tcbs, const uint8_t
         if ((!live || live[i]) && tcbs[i].state >= RXG_TCP_STATES)
             return fail(-EINVAL, "rxg_tcb_load: slot %d state %u", i, tcbs[i].state);
     c->mir.load(tcbs, live, ntcb);
-    c->dirty = true;
+    c->tables.tcb_changed();
     c->touched_all = true;
     c->gen++;
     c->rcv_cur.clear();
@@ -286,7 +276,7 @@ extern "C" int rxg_flow_partition(rxg_ctx *c, uint32_t part, uint32_t nparts)
     c->mir.part = part;
     c->mir.nparts = nparts;
     c->mir.need_rebuild = true;  // the whole table, as after rxg_tcb_load
-    c->dirty = true;
+    c->tables.tcb_changed();
     c->touched_all = true;
     c->gen++;
     return 0;
@@ -348,175 +338,78 @@ extern "C" int rxg_tcb_sync(rxg_ctx *c)
     if (!c) return fail(-EINVAL, "rxg_tcb_sync: ctx NULL");
     const int rc = rxg_tcb_drain(c);
     if (rc < 0) return rc;
-    return c->dirty ? tcb_push(c) : 0;
+    return tcb_push(c);
 }
 
-// Before a mirror write on c->stream: kernels that read the tables on other streams are
-// done.  Lazy mode records the event now, on the reader's stream (it covers every launch the
-// stream has taken so far, the table readers among them).
-static int wait_table_readers(rxg_ctx *c)
+int tcb_push(rxg_ctx *c)
 {
-    for (auto &r : c->readers)
-        if (r.pending) {
-            if (!r.recorded) HIP_OK(hipEventRecord(r.e, r.s));
-            HIP_OK(hipStreamWaitEvent(c->stream, r.e, 0));
-            r.pending = r.recorded = false;
-        }
+    if (!c->tables.tcb_stale()) return 0;
+    if (int rc = set_device(c)) return rc;
+    return c->tables.sync(&c->mir, nullptr, false);
+}
+
+// ------------------------------------------------- the tables' device side (HipTablePort) ---
+int HipTablePort::event_create(Event *e, bool reader)
+{
+    // a reader's event, device-scope release: it orders streams of this device (and the host's
+    // wait before a buffer is freed); no system-scope cache write-back
+    HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming | (reader ? hipEventReleaseToDevice : 0u)));
     return 0;
 }
 
-// Before device table buffers are freed or reallocated: every reader has finished (host wait).
-static int sync_table_readers(rxg_ctx *c)
+void HipTablePort::event_destroy(Event e) { (void)hipEventDestroy(e); }
+
+int HipTablePort::record(Event e, Stream s) { HIP_OK(hipEventRecord(e, s)); return 0; }
+
+int HipTablePort::stream_wait(Stream s, Event e) { HIP_OK(hipStreamWaitEvent(s, e, 0)); return 0; }
+
+int HipTablePort::host_wait(Event e) { HIP_OK(hipEventSynchronize(e)); return 0; }
+
+int HipTablePort::sync() { HIP_OK(hipStreamSynchronize(c->stream)); return 0; }
+
+// device memory the host writes through a large BAR, else pinned host memory read over PCIe
+int HipTablePort::patch_alloc(MirrorPatch **p, uint32_t cap, bool dev)
 {
-    for (auto &r : c->readers)
-        if (r.pending) {
-            if (!r.recorded) HIP_OK(hipEventRecord(r.e, r.s));
-            HIP_OK(hipEventSynchronize(r.e));
-            r.pending = r.recorded = false;
-        }
+    const size_t bytes = (size_t)cap * sizeof(MirrorPatch);
+    if (dev)
+        HIP_OK(hipExtMallocWithFlags((void **)p, bytes, hipDeviceMallocFinegrained));
+    else
+        HIP_OK(hipHostMalloc((void **)p, bytes, hipHostMallocDefault));
     return 0;
 }
 
-// A patch list in c->patch[bi] (n patches) as its own launch on c->stream.
-static int launch_patch_list(rxg_ctx *c, int bi, uint32_t n)
+int HipTablePort::patch_free(MirrorPatch *p, bool dev)
 {
-    rxg_ctx::PatchBuf &pb = c->patch[bi];
-    int rc = wait_table_readers(c);
-    if (rc) return rc;
+    HIP_OK(dev ? hipFree(p) : hipHostFree(p));
+    return 0;
+}
+
+void HipTablePort::patch_write(MirrorPatch *dst, const MirrorPatch *src, uint32_t n, bool dev)
+{
+    std::memcpy(dst, src, (size_t)n * sizeof(MirrorPatch));
+    if (dev) bar_publish(c, &dst[n - 1].v[3]);  // through the BAR: out before the launch
+}
+
+int HipTablePort::patch_launch(const MirrorPatch *list, uint32_t n, const DevBuf &buckets, const DevBuf &listen,
+                               const DevBuf &arp)
+{
     // the last replay's counter corrections ride along (its table writes are why this runs)
     CounterDelta d;
     if (c->pend) std::memcpy(d.v, c->pend_delta, sizeof d.v);
-    HIP_OK(launch_mirror_patch(pb.h, n, (uint4 *)c->buckets.p, (int32_t *)c->listen.p, (uint32_t *)c->d_arp.p,
-                               c->stream, c->pend ? correction_row(c) : nullptr, &d));
+    HIP_OK(launch_mirror_patch(list, n, (uint4 *)buckets.p, (int32_t *)listen.p, (uint32_t *)arp.p, c->stream,
+                               c->pend ? correction_row(c) : nullptr, &d));
     if (c->pend) {
         std::memset(c->pend_delta, 0, sizeof c->pend_delta);
         c->pend = false;
     }
-    HIP_OK(hipEventRecord(pb.ev, c->stream));
-    pb.set = true;
-    HIP_OK(hipEventRecord(c->mirror_ev, c->stream));
-    c->mirror_ev_set = true;
-    // a list a burst is still to carry (this launch was another table's overflow,
-    // apply_patches) is written after this recording: the event is re-recorded after that
-    // burst (mirror_event), as the rebuild paths do
-    c->mirror_ev_stale = c->ip_n != 0;
     return 0;
 }
 
-// A mirror's patches (at most one per device word): into the next patch buffer, then in one
-// launch on c->stream -- or, when the caller is about to launch a burst on c->stream that
-// can carry them (c->defer_patch, launch_bursts), left for that launch (c->ip_*).
-template <typename M>
-static int apply_patches(rxg_ctx *c, M &mirror)
-{
-    const std::vector<MirrorPatch> &p = mirror.patches;
-    if (p.empty()) return 0;
-    const uint32_t n = (uint32_t)p.size();
-    uint32_t tables = 0;
-    for (const MirrorPatch &q : p) tables |= 1u << q.target;
-    if (c->defer_patch && c->ip_n != 0) {
-        // a second table's patches (the ARP mirror's after the TCB mirror's) join the list
-        // the burst carries, when it has room (the kernel applies each by its target).  Every
-        // workgroup of the carrying launch stores the whole list in parallel, so no two of its
-        // patches may write one word: a mirror emits at most one patch per word, and only a
-        // list for tables the carried one does not touch joins it.
-        rxg_ctx::PatchBuf &cb = c->patch[c->ip_buf];
-        if ((c->ip_tables & tables) == 0 && c->ip_n + n <= kLaunchPatchMax && c->ip_n + n <= cb.cap) {
-            std::memcpy(cb.h + c->ip_n, p.data(), (size_t)n * sizeof(MirrorPatch));
-            bar_publish(c, &cb.h[c->ip_n + n - 1].v[3]);
-            mirror.patches_taken();
-            ++c->table_writes;
-            c->ip_n += n;
-            c->ip_tables |= tables;
-            return 0;
-        }
-    }
-    const int bi = c->patch_next;
-    rxg_ctx::PatchBuf &pb = c->patch[bi];
-    c->patch_next = (bi + 1) % rxg_ctx::kPatchBufs;
-    if (pb.set) HIP_OK(hipEventSynchronize(pb.ev));  // the launch that read this buffer is done
-    pb.set = false;
-    if (n > pb.cap) {
-        if (pb.h) HIP_OK(c->patch_dev ? hipFree(pb.h) : hipHostFree(pb.h));
-        pb.h = nullptr;
-        pb.cap = 0;
-        const uint32_t cap = std::max<uint32_t>(n * 2u, 1024u);
-        const size_t bytes = (size_t)cap * sizeof(MirrorPatch);
-        if (c->patch_dev)
-            HIP_OK(hipExtMallocWithFlags((void **)&pb.h, bytes, hipDeviceMallocFinegrained));
-        else
-            HIP_OK(hipHostMalloc((void **)&pb.h, bytes, hipHostMallocDefault));
-        pb.cap = cap;
-    }
-    std::memcpy(pb.h, p.data(), (size_t)n * sizeof(MirrorPatch));
-    if (c->patch_dev) bar_publish(c, &pb.h[n - 1].v[3]);  // through the BAR: out before the launch
-    mirror.patches_taken();
-    ++c->table_writes;
-    if (c->defer_patch && c->ip_n == 0 && n <= kLaunchPatchMax) {
-        c->ip_list = pb.h;
-        c->ip_n = n;
-        c->ip_buf = bi;
-        c->ip_tables = tables;
-        c->mirror_ev_set = true;
-        c->mirror_ev_stale = true;  // the carrying launch is the write (mirror_event)
-        return 0;
-    }
-    return launch_patch_list(c, bi, n);
-}
+int HipTablePort::table_resize(DevBuf &b, size_t bytes) { return ensure(b, bytes); }
 
-// A carried list the burst did not take (a failure between the sync and the launch): as its
-// own launch, so no write is lost.
-static int launch_carried_patches(rxg_ctx *c)
+int HipTablePort::table_upload(DevBuf &b, const void *src, size_t bytes)
 {
-    if (c->ip_n == 0) return 0;
-    const uint32_t n = c->ip_n;
-    c->ip_n = 0;
-    return launch_patch_list(c, c->ip_buf, n);
-}
-
-int mirror_event(rxg_ctx *c)
-{
-    if (c->ip_n) return launch_carried_patches(c);  // (not between a sync and its burst)
-    if (!c->mirror_ev_stale) return 0;
-    HIP_OK(hipEventRecord(c->mirror_ev, c->stream));
-    c->mirror_ev_stale = false;
-    return 0;
-}
-
-// Bring the device TCB mirror up to date: the changed words (usual) or, after a load or
-// past load 1/2, the whole table.  No host block on the patch path.
-int tcb_push(rxg_ctx *c)
-{
-    if (!c->dirty) return 0;
-    int rc = set_device(c);
-    if (rc) return rc;
-    TcbMirror &m = c->mir;
-    if (m.need_rebuild) {
-        m.rebuild();
-        const size_t sb = m.slots.size() * sizeof(Slot), lb = m.listen.size() * sizeof(int32_t);
-        if (sb > c->buckets.bytes || lb > c->listen.bytes) {
-            // the old buffers must be idle before they are freed
-            if ((rc = sync_table_readers(c))) return rc;
-            HIP_OK(hipStreamSynchronize(c->stream));
-            if ((rc = ensure(c->buckets, sb))) return rc;
-            if ((rc = ensure(c->listen, lb))) return rc;
-        }
-        if ((rc = wait_table_readers(c))) return rc;
-        HIP_OK(hipMemcpyAsync(c->buckets.p, m.slots.data(), sb, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->listen.p, m.listen.data(), lb, hipMemcpyHostToDevice, c->stream));
-        // the next write changes m.slots in place: the copies must have consumed them
-        HIP_OK(hipStreamSynchronize(c->stream));
-        HIP_OK(hipEventRecord(c->mirror_ev, c->stream));
-        c->mirror_ev_set = true;
-        c->mirror_ev_stale = c->ip_n != 0;  // (a list a burst is to carry comes after it)
-        ++c->table_writes;
-    } else if ((rc = apply_patches(c, m))) {
-        return rc;
-    }
-    c->bucket_mask = m.nb - 1;
-    c->dev_ntcb = m.ntcb();
-    c->dev_min_null = m.min_null;
-    c->dirty = false;
+    HIP_OK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 
@@ -525,7 +418,7 @@ extern "C" int rxg_arp_learned(rxg_ctx *c, uint32_t ip)
 {
     if (!c) return fail(-EINVAL, "rxg_arp_learned: ctx NULL");
     c->arp_enabled = true;
-    if (c->arp.add(ip)) c->arp_dirty = true;
+    if (c->arp.add(ip)) c->tables.arp_changed();
     c->arp_since_burst.emplace(ip, 1);
     return 0;
 }
@@ -536,7 +429,7 @@ extern "C" int rxg_arp_load(rxg_ctx *c, const uint32_t *ips, uint32_t n)
     c->arp_enabled = true;
     c->arp.clear();
     for (uint32_t i = 0; i < n; ++i) c->arp.add(ips[i]);
-    c->arp_dirty = true;
+    c->tables.arp_changed();
     return 0;
 }
 
@@ -548,133 +441,23 @@ extern "C" int rxg_arp_disable(rxg_ctx *c)
     c->arp_enabled = false;
     c->arp.clear();
     c->arp_since_burst.clear();
-    c->arp_dirty = true;
-    return 0;
-}
-
-static int arp_sync(rxg_ctx *c)
-{
-    if (!c->arp_enabled || !c->arp_dirty) return 0;
-    ArpMirror &a = c->arp;
-    int rc;
-    if (a.need_rebuild) {
-        a.rebuild();
-        const size_t bytes = a.slots.size() * 4;
-        if (bytes > c->d_arp.bytes) {
-            if ((rc = sync_table_readers(c))) return rc;
-            HIP_OK(hipStreamSynchronize(c->stream));
-            if ((rc = ensure(c->d_arp, bytes))) return rc;
-        }
-        if ((rc = wait_table_readers(c))) return rc;
-        HIP_OK(hipMemcpyAsync(c->d_arp.p, a.slots.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        HIP_OK(hipEventRecord(c->mirror_ev, c->stream));
-        c->mirror_ev_set = true;
-        c->mirror_ev_stale = c->ip_n != 0;  // (a list a burst is to carry comes after it)
-        ++c->table_writes;
-    } else if ((rc = apply_patches(c, a))) {
-        return rc;
-    }
-    c->arp_mask = a.nb - 1;
-    c->arp_dirty = false;
-    return 0;
-}
-
-// A launch on `st` that reads the mirror tables: it follows the last mirror write, and
-// the next mirror write follows it.
-static bool stream_registered(const rxg_ctx *c, hipStream_t st)
-{
-    return std::find(c->registered.begin(), c->registered.end(), st) != c->registered.end();
-}
-
-static int order_table_reader_before(rxg_ctx *c, hipStream_t st)
-{
-    if (st == c->stream) return 0;
-    // RXG_CFG_STREAMS_OUTLIVE_WRITES: the next write records an event on `st`, so `st` must
-    // still exist then; only a registered stream is known to (rxg_stream_retire ends that)
-    if (c->lazy_readers && !stream_registered(c, st))
-        return fail(-EINVAL, "table-reading launch on stream %p, not registered with rxg_stream_register "
-                             "(RXG_CFG_STREAMS_OUTLIVE_WRITES)", (void *)st);
-    if (!c->mirror_ev_set) return 0;
-    // a stream that already waited for the current mirror_ev needs no second wait (each wait
-    // is a barrier packet between the caller's launches)
-    for (auto &x : c->readers)
-        if (x.s == st && x.waited == c->table_writes) return 0;
-    if (int rc = mirror_event(c)) return rc;  // (a write a burst carried: recorded now)
-    HIP_OK(hipStreamWaitEvent(st, c->mirror_ev, 0));
-    for (auto &x : c->readers)
-        if (x.s == st) x.waited = c->table_writes;
-    return 0;
-}
-
-static constexpr size_t kMaxReaderStreams = 16;
-
-static int order_table_reader_after(rxg_ctx *c, hipStream_t st)
-{
-    if (st == c->stream) return 0;
-    rxg_ctx::Reader *r = nullptr;
-    for (auto &x : c->readers)
-        if (x.s == st) r = &x;
-    if (!r) {
-        for (auto &x : c->readers)
-            if (!x.pending) { r = &x; break; }
-        if (!r && c->readers.size() >= kMaxReaderStreams) {
-            // more reader streams than entries: the next write's stream waits for them now
-            int rc = wait_table_readers(c);
-            if (rc) return rc;
-            r = &c->readers[0];
-        }
-        if (!r) {
-            // device-scope release: these events order streams of this device (and the
-            // host's wait before a buffer is freed); no system-scope cache write-back
-            hipEvent_t e;
-            HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice));
-            c->readers.push_back({st, e, false, false, ~0ull});
-            r = &c->readers.back();
-        }
-        // order_table_reader_before found no entry for st, so it has just waited for the
-        // current mirror_ev
-        r->waited = c->mirror_ev_set ? c->table_writes : ~0ull;
-        r->s = st;
-    }
-    r->pending = true;
-    if (c->lazy_readers) {
-        r->recorded = false;  // recorded by the next write (wait_table_readers)
-    } else {
-        HIP_OK(hipEventRecord(r->e, st));
-        r->recorded = true;
-    }
+    c->tables.arp_changed();
     return 0;
 }
 
 extern "C" int rxg_stream_register(rxg_ctx *c, void *stream)
 {
     if (!c || !stream) return fail(-EINVAL, "rxg_stream_register: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (st != c->stream && !stream_registered(c, st)) c->registered.push_back(st);
+    c->tables.register_stream((hipStream_t)stream);
     return 0;
 }
 
 extern "C" int rxg_stream_retire(rxg_ctx *c, void *stream)
 {
     if (!c || !stream) return fail(-EINVAL, "rxg_stream_retire: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (st == c->stream) return 0;
-    int rc = set_device(c);
-    if (rc) return rc;
-    // the order the next table write needs against this stream's launches, taken now; the
-    // entry then names no stream (a new stream may get the same handle)
-    for (auto &r : c->readers)
-        if (r.s == st) {
-            if (r.pending && !r.recorded) {
-                HIP_OK(hipEventRecord(r.e, st));
-                r.recorded = true;
-            }
-            r.s = nullptr;
-            r.waited = ~0ull;
-        }
-    c->registered.erase(std::remove(c->registered.begin(), c->registered.end(), st), c->registered.end());
-    return 0;
+    if ((hipStream_t)stream == c->stream) return 0;
+    if (int rc = set_device(c)) return rc;
+    return c->tables.retire((hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------- bursts ---
@@ -691,13 +474,12 @@ void select_burst(rxg_ctx *c, uint32_t j)
     c->pm_n = 0;  // a gather describes the burst it followed
 }
 
-// Classify bursts[0..k) of one frame pool against the mirror as it stands: one launch per
-// kMaxBursts bursts.  The bursts are then replayed in order (rxg_rx_replay).
 // Validation, mirror sync and the replay bookkeeping of a burst set (launched or served).
 // stride64 != 0: fixed-stride bursts (rxg_rx_bursts_strided_dev): bursts[j].off64 is unused and
-// bursts[j].pad holds the burst's first slot.
+// bursts[j].pad holds the burst's first slot.  carry: a launch on the context's stream follows
+// and can take the mirrors' patch list (launch_bursts).
 int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, uint32_t k, uint32_t rec_kind,
-                 const char *who, uint32_t stride64)
+                 const char *who, uint32_t stride64, bool carry)
 {
     // a rejected launch leaves nothing to replay: rxg_rx_replay refuses until a burst succeeds
     c->burst_ok = false;
@@ -722,15 +504,13 @@ int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, ui
     }
     if (any && !frames) return fail(-EINVAL, "%s: NULL frame pool", who);
     if (any && ((uintptr_t)frames & 15u)) return fail(-EINVAL, "%s: frame pool not 16-byte aligned", who);
-    c->burst_ok = false;
     int rc = set_device(c);
     if (rc) return rc;
-    if ((rc = rxg_tcb_sync(c))) return rc;
-    if ((rc = arp_sync(c))) return rc;
+    if ((rc = rxg_tcb_drain(c)) < 0) return rc;  // posted writes first, then the device tables
+    if ((rc = c->tables.sync(&c->mir, c->arp_enabled ? &c->arp : nullptr, carry))) return rc;
     c->arp_since_burst.clear();
     c->last_frames = (const uint8_t *)frames;
     c->last_stride = rec_kind;
-    c->last_bursts.clear();
     for (uint32_t j = 0; j < k; ++j)
         c->last_bursts.push_back({stride64 ? nullptr : bursts[j].off64, bursts[j].len, bursts[j].n,
                                   (const uint8_t *)bursts[j].out, stride64 ? bursts[j].pad : 0u, stride64});
@@ -746,6 +526,8 @@ int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, ui
     return 0;
 }
 
+// Classify bursts[0..k) of one frame pool against the mirror as it stands: one launch per
+// kMaxBursts bursts.  The bursts are then replayed in order (rxg_rx_replay).
 static int launch_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, uint32_t k, uint32_t rec_kind,
                          void *stream, const char *who, uint32_t stride64 = 0,
                          const rxg_payload_slots *pay = nullptr)
@@ -753,26 +535,22 @@ static int launch_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bu
     hipStream_t st = pick(c, stream);
     // an unregistered stream is refused before anything changes (rxg.h: "-EINVAL, nothing
     // launched"): no mirror sync, and the previous burst stays replayable
-    if (c->lazy_readers && st != c->stream && !stream_registered(c, st))
+    if (!c->tables.reader_allowed(st))
         return fail(-EINVAL, "%s: table-reading launch on stream %p, not registered with rxg_stream_register "
                              "(RXG_CFG_STREAMS_OUTLIVE_WRITES)", who, (void *)st);
     // The burst's first launch carries the mirror's patch list when nothing else reads the
     // tables meanwhile: launched on the context's stream (ordered after every earlier reader
-    // there), no reader pending on another stream, and frames in that launch (a launch of
-    // none is never made).  It then replaces a patch launch: ≈ 10 µs of host launch latency
-    // per churning burst.
+    // there), no reader pending on another stream (TableSync::sync sees to that), and frames
+    // in that launch (a launch of none is never made).  It then replaces a patch launch: ≈ 10 µs
+    // of host launch latency per churning burst.
     bool first_has_frames = false;
     for (uint32_t j = 0; j < std::min(k, kMaxBursts); ++j) first_has_frames |= bursts[j].n != 0;
-    bool others_pending = false;
-    for (const auto &r : c->readers) others_pending |= r.pending;
-    c->defer_patch = c->patch_dev && st == c->stream && first_has_frames && !others_pending;
-    int rc = begin_bursts(c, frames, bursts, k, rec_kind, who, stride64);
-    c->defer_patch = false;
+    int rc = begin_bursts(c, frames, bursts, k, rec_kind, who, stride64, st == c->stream && first_has_frames);
     if (rc) {
-        (void)launch_carried_patches(c);
+        (void)c->tables.abandon();
         return rc;
     }
-    if ((rc = order_table_reader_before(c, st))) return rc;
+    if ((rc = c->tables.before(st))) return rc;
     LaunchBurst lb[kMaxBursts];
     for (uint32_t j0 = 0; j0 < k; j0 += kMaxBursts) {
         const uint32_t m = std::min(kMaxBursts, k - j0);
@@ -793,27 +571,16 @@ static int launch_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bu
         }
         L.counters = c->counters;
         // (the by-reference hand-off writes no payload: its kernel's occupancy grid)
-        L.max_blocks = c->max_blocks ? c->max_blocks : pay && pay->arena ? c->grid_pay
-                     : pay ? (rec_kind == RXG_REC48 ? c->grid_ref48 : rec_kind == RXG_REC8 ? c->grid_ref8 : c->grid_ref16)
-                     : (rec_kind == RXG_REC48 ? c->grid_rec48 : rec_kind == RXG_REC8 ? c->grid_rec8 : c->grid_rec16);
-        if (L.max_blocks == 0) L.max_blocks = 1024;
-        const bool carries = j0 == 0 && c->ip_n != 0;
-        if (carries) {
-            L.ipatch = c->ip_list;
-            L.nipatch = c->ip_n;
-        }
+        L.max_blocks = pay && pay->arena && !c->max_blocks ? c->grid_pay : grid_for(c, rec_kind, pay != nullptr);
+        L.ipatch = c->tables.carried(&L.nipatch);  // (the first launch takes it)
         const hipError_t e = launch_rx(L, st);
         if (e != hipSuccess) {
-            (void)launch_carried_patches(c);
+            (void)c->tables.abandon();
             HIP_OK(e);
         }
-        if (carries) {  // the list's buffer is free again once this launch has run
-            c->ip_n = 0;
-            HIP_OK(hipEventRecord(c->patch[c->ip_buf].ev, st));
-            c->patch[c->ip_buf].set = true;
-        }
+        if (L.nipatch && (rc = c->tables.carried_taken(st))) return rc;
     }
-    if ((rc = order_table_reader_after(c, st))) return rc;
+    if ((rc = c->tables.after(st))) return rc;
     c->burst_ok = true;
     if (pay && k == 1 && bursts[0].n) {
         // rxg_payload_take answers from this burst's messages (fetched at its first call)
@@ -924,8 +691,7 @@ extern "C" int rxg_tx_cksum_dev(rxg_ctx *c, const rxg_dev_tx_batch *b, void *str
     L.nbursts = 1;
     L.mode = 0;
     L.counters = nullptr;
-    L.max_blocks = c->max_blocks ? c->max_blocks : c->grid_tx;
-    if (L.max_blocks == 0) L.max_blocks = 1024;
+    L.max_blocks = grid_for(c, 0);
     HIP_OK(launch_rx(L, pick(c, stream)));
     return 0;
 }
@@ -963,8 +729,8 @@ extern "C" int rxg_counters_read(rxg_ctx *c, uint64_t *out)
     if (int rc = set_device(c)) return rc;
     if (int rc = flush_delta(c)) return rc;
     // bursts on caller streams add to the block too: every one launched so far is waited for
-    // (the table readers' events, sync_table_readers), then the context's stream
-    if (int rc = sync_table_readers(c)) return rc;
+    // (the table readers' events), then the context's stream
+    if (int rc = c->tables.wait_readers(true)) return rc;
     HIP_OK(hipStreamSynchronize(c->stream));
     std::vector<uint64_t> rows((size_t)RXG_COUNTER_ROWS * RXG_NCOUNTERS);
     HIP_OK(hipMemcpyAsync(rows.data(), c->counters, kCounterBytes, hipMemcpyDeviceToHost, c->stream));

@@ -213,7 +213,7 @@ static int reclassify(rxg_ctx *c, const std::vector<uint32_t> &sel, std::vector<
         return fail(-EINVAL, "rxg_rx_replay: no burst on this context to re-classify against");
     if ((rc = ensure(c->d_sel, sel.size() * 4))) return rc;
     if ((rc = ensure(c->d_fix, sel.size() * sizeof(rxg_rec16)))) return rc;
-    if (c->dirty && (rc = tcb_push(c))) return rc;
+    if ((rc = tcb_push(c))) return rc;
     HIP_OK(hipMemcpyAsync(c->d_sel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, c->stream));
     const LaunchBurst one{off64, c->last_len, (uint32_t)sel.size(), (uint8_t *)c->d_fix.p, 0u};
     LaunchRx L;
@@ -225,7 +225,7 @@ static int reclassify(rxg_ctx *c, const std::vector<uint32_t> &sel, std::vector<
     L.mode = RXG_REC16;
     L.table = table_view(c);
     L.counters = nullptr;  // corrections go to the host row instead
-    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_rec16 ? c->grid_rec16 : 1024);
+    L.max_blocks = grid_for(c, RXG_REC16);
     HIP_OK(launch_rx(L, c->stream));
     out.resize(sel.size());
     HIP_OK(hipMemcpyAsync(out.data(), c->d_fix.p, sel.size() * sizeof(rxg_rec16), hipMemcpyDeviceToHost, c->stream));

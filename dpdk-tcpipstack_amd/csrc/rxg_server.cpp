@@ -259,11 +259,8 @@ static int server_burst(rxg_ctx *c, const rxg_dev_batch *b, bool inl, bool large
     int rc = begin_bursts(c, b->frames, &one, 1, b->rec_kind, "rxg_server_burst_dev");
     if (rc) return rc;
     // mirror writes queued on the context's stream land before the server reads the tables
-    if (c->table_writes != c->srv.synced_writes) {
-        if ((rc = mirror_event(c))) return rc;  // (a write a burst carried: recorded now)
-        HIP_OK(hipEventSynchronize(c->mirror_ev));
-        c->srv.synced_writes = c->table_writes;
-    }
+    // (one a burst carried among them: its event is recorded now)
+    if ((rc = c->tables.host_wait_writes(&c->srv.synced_writes))) return rc;
     if (b->n) {
         SrvReq r;
         std::memset(&r, 0, sizeof r);
