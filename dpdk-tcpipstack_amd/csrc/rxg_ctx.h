@@ -84,6 +84,7 @@ struct rxg_ctx {
     hipStream_t stream = nullptr;
     uint32_t max_blocks = 0;        // rxg_config.max_blocks: grid cap (0 = occupancy grid)
     uint32_t grid_pay = 512;        // rxg_rx_burst_payload_dev's grid (set at init)
+    uint32_t grid_txb = 0;          // rxg_tx_build_dev's occupancy grid (set at init)
     // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
     uint32_t grid[2][4] = {};
     rxg::PackPool pack_pool;  // rxg_rx_burst's packing threads

@@ -83,6 +83,7 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         // (8 waves) measured faster than the occupancy grid's 3 (C3 621 against 627 us, C4 174
         // against 177)
         c->grid_pay = cus * 2u;
+        c->grid_txb = cus * (uint32_t)tx_build_blocks_per_cu();  // rxg_tx_build_dev's occupancy grid
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -693,6 +694,45 @@ extern "C" int rxg_tx_cksum_dev(rxg_ctx *c, const rxg_dev_tx_batch *b, void *str
     L.counters = nullptr;
     L.max_blocks = grid_for(c, 0);
     HIP_OK(launch_rx(L, pick(c, stream)));
+    return 0;
+}
+
+static_assert(sizeof(rxg_tx_flow) == 32 && sizeof(rxg_tx_seg) == 32 && sizeof(rxg_dev_tx_build) == 80,
+              "transmit segment build layouts");
+
+extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_tx_build_dev: NULL argument");
+    if (b->n == 0) return 0;
+    if (!b->payload || !b->flows || !b->segs || !b->frames || !b->len)
+        return fail(-EINVAL, "rxg_tx_build_dev: NULL device pointer");
+    if (((uintptr_t)b->payload & 15u) || ((uintptr_t)b->frames & 63u) || ((uintptr_t)b->segs & 7u) ||
+        ((uintptr_t)b->flows & 7u) || ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) ||
+        ((uintptr_t)b->stats & 7u))
+        return fail(-EINVAL, "rxg_tx_build_dev: payload needs 16-byte, frames 64-byte, segs, flows and stats "
+                             "8-byte, off64 4-byte, len 2-byte alignment");
+    if (!b->off64) {
+        if (!b->stride64) return fail(-EINVAL, "rxg_tx_build_dev: stride64 0");
+        if ((uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
+            return fail(-EINVAL, "rxg_tx_build_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    LaunchTxBuild L;
+    L.payload = (const uint8_t *)b->payload;
+    L.payload_bytes = b->payload_bytes;
+    L.flows = b->flows;
+    L.nflows = b->nflows;
+    L.n = b->n;
+    L.segs = b->segs;
+    L.frames = (uint8_t *)b->frames;
+    L.off64 = b->off64;
+    L.slot0 = b->slot0;
+    L.stride64 = b->stride64;
+    L.len = b->len;
+    L.stats = (unsigned long long *)b->stats;
+    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txb ? c->grid_txb : 1024u);  // (as grid_for)
+    HIP_OK(launch_tx_build(L, pick(c, stream)));
     return 0;
 }
 

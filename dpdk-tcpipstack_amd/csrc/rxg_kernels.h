@@ -158,6 +158,23 @@ hipError_t launch_server(const LaunchServer &L, hipStream_t st);
 // rxg_payload.hip: gather of the burst's candidate payloads (one launch + a memset)
 hipError_t launch_payload(const LaunchPayload &P, hipStream_t st, uint32_t *tickets_used);
 uint32_t payload_blocks(uint32_t n);
+// rxg_txbuild.hip: transmit segment build (rxg_tx_build_dev), one launch
+struct LaunchTxBuild {
+    const uint8_t *payload;
+    uint64_t payload_bytes;
+    const rxg_tx_flow *flows;
+    uint32_t nflows;
+    uint32_t n;
+    const rxg_tx_seg *segs;
+    uint8_t *frames;
+    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
+    uint32_t slot0, stride64;
+    uint16_t *len;
+    unsigned long long *stats;  // {built, skipped}, added to; may be nullptr
+    uint32_t max_blocks;        // grid cap (grid-stride over 64-segment slices); 0 = none
+};
+hipError_t launch_tx_build(const LaunchTxBuild &B, hipStream_t st);
+int tx_build_blocks_per_cu();  // resident 256-thread workgroups per CU of its kernel
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

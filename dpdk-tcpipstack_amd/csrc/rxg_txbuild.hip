@@ -1,0 +1,399 @@
+// rxg_txbuild.hip — transmit segment build on the device (rxg_tx_build_dev).
+//
+// What the reference does per segment on the CPU -- sendtcpdata (tcp_out.c:157-207: get a
+// buffer, add_tcp_data's memcpy of the payload, the TCP header) -> ip_out (ip.c:86-118: the
+// IPv4 header, both checksums) -> ether_out (etherout.c:87-99: the Ethernet header) -- in one
+// pass over a batch of segment descriptors: each payload byte is loaded once from wherever the
+// socket data lives, each frame line is stored once with both checksums in place.
+//
+// A wave takes the launch's 64-descriptor slices wave, wave + nwaves, ...: lane i validates
+// descriptor i of the slice (a skipped descriptor's flow index and source offset are never
+// used as addresses), loads its flow record and writes len[i].  The slice's segments are
+// then built by size class, as rx_kernel's frames are (rxg_rx_frames.h run_class): a group
+// of LPF lanes per frame, 64 / LPF frames per round.
+//
+//   frame chunk c = frame bytes [16c, 16c + 16); a frame of data_len L has NC = 4 *
+//   ceil((54 + L) / 64) of them; chunk c >= 3 holds payload bytes [16c - 54, 16c - 38)
+//
+//   NC == 4 (L <= 10: pure ACKs, SYN, FIN)   4 lanes per frame, 16 frames per round: lane c
+//           writes chunk c; lane 3 loads the payload's one or two chunks itself
+//   NC <= 16 / 32 / 64 / 128 / more          4 / 8 / 16 / 32 / 64 lanes per frame; round r
+//           gives lane l chunk r * LPF + l: one 16-byte load of the aligned source chunk
+//           that holds the destination chunk's first byte, the following source chunk from
+//           the next lane (the group's last lane: from the first lane's load for the next
+//           round, which is issued before the current round is consumed), a byte funnel
+//           shift by (src_off - 6) mod 16, the tail masked to zero, the chunk's 16-bit
+//           words added to the lane's sum (v_dot2_u32_u16), one 16-byte non-temporal store.
+//
+// Every store instruction of a group writes whole 64-byte lines (LPF >= 4, NC a multiple of
+// 4).  The first line (the 54 header bytes and payload bytes 0-9) is kept in the registers of
+// the group's lanes 0-3 and stored last, when the group's sum has given the TCP checksum.
+// Lanes past the frame's end, and the last round's look-ahead, load the payload's last chunk
+// again (first chunk: lanes 0-2 of round 0): loads are issued unconditionally, as
+// rxg_rx_frames.h's are and for its reason.  Nothing outside the chunks overlapping the
+// payload is read.  What the repeats cost in memory traffic is not separated: the counted
+// read traffic of 2^20 x 1460 B segments is 1.18x the algorithmic read bytes,
+// which also holds the memory lines at a segment's two ends that its neighbours' groups
+// fetch as well; that the repeats themselves are served by the CU's cache is supposed.
+//
+// Roofline: HBM, algorithmic bytes per segment = data_len (read) + 32 (descriptor) +
+// 64 * ceil((54 + data_len) / 64) (written) + 2 (len).
+#include "rxg_kernels.h"
+
+namespace rxg {
+namespace {
+
+constexpr uint32_t kHdr = 54;  // Ethernet 14 + IPv4 20 + TCP 20 (data_off 0x50, no options)
+
+struct TbArgs {
+    const uint8_t *payload;
+    uint64_t payload_bytes;
+    const rxg_tx_flow *flows;
+    const rxg_tx_seg *segs;
+    uint8_t *frames;
+    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
+    uint16_t *len;
+    unsigned long long *stats;
+    uint32_t nflows, n, slot0, stride64, nslices;
+};
+
+// A segment's descriptor and flow record as its lane (and, broadcast, its group) holds them.
+struct Seg {
+    uint32_t s_lo, s_hi;  // src_off
+    uint32_t lw;          // data_len | win_raw << 16
+    uint32_t seq, ack;
+    uint32_t idf;         // ip_id | tcp_flags << 16
+    uint32_t off;         // 64-byte slot of the frame
+    uint32_t ports;       // dport | sport << 16
+    uint32_t ip_src_raw;  // rxg_tx_flow.ipv4_dst: the frame's src_addr as stored
+    uint32_t ip_dst_host; // rxg_tx_flow.ipv4_src: htonl() of it is the frame's dst_addr
+    uint32_t m0, m1, m2;  // frame bytes 0-11: dst MAC, src MAC
+};
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint4 ld16(const uint8_t *p)
+{
+    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ void st16(uint8_t *p, uint4 o)
+{
+    u32x4 v;
+    v.x = o.x; v.y = o.y; v.z = o.z; v.w = o.w;
+    __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
+}
+
+__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src_lane)
+{
+    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
+}
+
+__device__ __forceinline__ uint32_t hsum(uint32_t d) { return (d & 0xFFFFu) + (d >> 16); }
+
+// acc + lo16(x) + hi16(x)  (rxg_rx_frames.h dsum)
+__device__ __forceinline__ uint32_t dsum(uint32_t x, uint32_t acc)
+{
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, x), __builtin_bit_cast(u16x2, 0x00010001u), acc, false);
+}
+
+// lane l <- lane l + K of the same row of 16 lanes (0 past the row's end)
+template <int K>
+__device__ __forceinline__ uint32_t dpp_down(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + K, 0xF, 0xF, false);
+}
+
+// Sum of a group of LPF lanes (aligned at a multiple of LPF), valid in the group's first lane
+// (rxg_rx_frames.h group_sum).
+template <int LPF>
+__device__ __forceinline__ uint32_t group_sum(uint32_t t, int lane)
+{
+    if constexpr (LPF >= 2) t += dpp_down<1>(t);
+    if constexpr (LPF >= 4) t += dpp_down<2>(t);
+    if constexpr (LPF >= 8) t += dpp_down<4>(t);
+    if constexpr (LPF >= 16) t += dpp_down<8>(t);
+    if constexpr (LPF >= 64) t += lane_read(t, (lane + 32) & 63);  // rows 0+2, 1+3
+    if constexpr (LPF >= 32) t += lane_read(t, (lane + 16) & 63);
+    return t;
+}
+
+// bytes [sh, sh + 16) of the 32-byte string lo || hi (rxg_payload.hip funnel16)
+__device__ __forceinline__ uint4 funnel16(uint4 lo, uint4 hi, uint32_t sh)
+{
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t ds = sh >> 2, bs = sh & 3u;
+    uint32_t s[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t)
+        s[t] = ds == 0 ? w[t] : ds == 1 ? w[t + 1] : ds == 2 ? w[t + 2] : w[t + 3];
+    uint4 r;
+    r.x = __builtin_amdgcn_alignbyte(s[1], s[0], bs);
+    r.y = __builtin_amdgcn_alignbyte(s[2], s[1], bs);
+    r.z = __builtin_amdgcn_alignbyte(s[3], s[2], bs);
+    r.w = __builtin_amdgcn_alignbyte(s[4], s[3], bs);
+    return r;
+}
+
+__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
+{
+    return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
+}
+
+// Frame chunk c >= 3 from the source chunks lo || hi: the payload bytes it holds, zero
+// elsewhere (frame bytes 48-53 of chunk 3, and bytes at or past 54 + L).
+__device__ __forceinline__ uint4 payload_chunk(uint4 lo, uint4 hi, uint32_t sh, uint32_t c, uint32_t L)
+{
+    uint4 o = sh ? funnel16(lo, hi, sh) : lo;
+    const int vb = (int)(kHdr + L) - (int)(16u * c);
+    if (vb < 16) {
+        o.x = keep_bytes(o.x, vb);
+        o.y = keep_bytes(o.y, vb - 4);
+        o.z = keep_bytes(o.z, vb - 8);
+        o.w = keep_bytes(o.w, vb - 12);
+    }
+    if (c == 3u) {
+        o.x = 0u;
+        o.y &= 0xFFFF0000u;
+    }
+    return o;
+}
+
+// Chunk c < 4 of the frame's first line: the headers of etherout.c:87-99, ip.c:97-118 and
+// tcp_out.c:174-193 with both checksums, `pay` the payload sum of the whole segment (16-bit
+// little-endian words) and p3 chunk 3's payload part (payload_chunk).
+__device__ __forceinline__ uint4 header_chunk(const Seg &g, uint32_t c, uint32_t pay, uint4 p3)
+{
+    const uint32_t L = g.lw & 0xFFFFu, win = g.lw >> 16;
+    const uint32_t ipid = g.idf & 0xFFFFu, flags = (g.idf >> 16) & 0xFFu;
+    const uint32_t dst = bswap32(g.ip_dst_host), src = g.ip_src_raw;
+    const uint32_t seq = bswap32(g.seq), ack = bswap32(g.ack);
+    const uint32_t sp = bswap16(g.ports & 0xFFFFu), dp = bswap16(g.ports >> 16);
+    // little-endian dwords of frame bytes 12.. : ether_type 08 00, version_ihl 0x45, tos 0
+    const uint32_t h3 = 0x00450008u;
+    const uint32_t h4 = bswap16((40u + L) & 0xFFFFu) | (ipid << 16);  // total_length, packet_id raw
+    const uint32_t h5 = 0x067F0000u;                                 // fragment_offset 0, ttl 127, proto 6
+    // both sums over little-endian 16-bit words; the stored field is the folded sum's
+    // complement as it stands (htons(calculate_checksum(..)), ip.c:107,118)
+    const uint32_t isum = 0x0045u + hsum(h4) + hsum(h5) + hsum(src) + hsum(dst);
+    const uint32_t ipck = (~fold16(isum)) & 0xFFFFu;
+    const uint32_t h11 = (ack >> 16) | (0x50u << 16) | (flags << 24);
+    // pseudo {src, dst, 0, 6, htons(20 + L)} || TCP header (cksum, urp 0) || payload
+    const uint32_t tsum = pay + hsum(src) + hsum(dst) + 0x0600u + bswap16((20u + L) & 0xFFFFu) + sp + dp +
+                          hsum(seq) + hsum(ack) + (h11 >> 16) + win;
+    const uint32_t tck = (~fold16(tsum)) & 0xFFFFu;
+    if (c == 0u) return make_uint4(g.m0, g.m1, g.m2, h3);
+    if (c == 1u) return make_uint4(h4, h5, ipck | (src << 16), (src >> 16) | (dst << 16));
+    if (c == 2u) return make_uint4((dst >> 16) | (sp << 16), dp | (seq << 16), (seq >> 16) | (ack << 16), h11);
+    return make_uint4(win | (tck << 16), p3.y, p3.z, p3.w);
+}
+
+// First source address the frame's chunk 3 takes bytes from, rounded down to 16 (may lie
+// before the payload's first chunk: loads are clamped to [lo, hi], the chunks that overlap
+// the payload), relative to the payload base.
+struct Span {
+    int64_t base, lo, hi;
+    uint32_t sh;
+};
+
+__device__ __forceinline__ Span span_of(const Seg &g)
+{
+    const uint64_t s = ((uint64_t)g.s_hi << 32) | g.s_lo;
+    const uint32_t L = g.lw & 0xFFFFu;
+    Span p;
+    p.base = ((int64_t)s - 6) & ~15ll;
+    p.lo = (int64_t)(s & ~15ull);
+    p.hi = (int64_t)((s + L - 1u) & ~15ull);  // (L > 0)
+    p.sh = (uint32_t)(s + 10u) & 15u;
+    return p;
+}
+
+// A frame of one line (L <= 10), 4 lanes: lane 3 loads what the payload touches.
+__device__ __forceinline__ void frame_small(const TbArgs &a, const Seg &g, int lane)
+{
+    const uint32_t c = (uint32_t)lane & 3u;
+    const uint32_t L = g.lw & 0xFFFFu;
+    uint4 p3 = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t pay = 0;
+    if (c == 3u && L != 0u) {
+        const Span p = span_of(g);
+        uint4 A = make_uint4(0u, 0u, 0u, 0u), N = A;
+        if (p.base >= p.lo) A = ld16(a.payload + p.base);
+        if (p.base + 16 >= p.lo && p.base + 16 <= p.hi) N = ld16(a.payload + p.base + 16);
+        p3 = payload_chunk(A, N, p.sh, 3u, L);
+        pay = hsum(p3.y) + hsum(p3.z) + hsum(p3.w);
+    }
+    st16(a.frames + (size_t)g.off * 64u + 16u * c, header_chunk(g, c, pay, p3));
+}
+
+template <int LPF>
+__device__ __forceinline__ void frame_stream(const TbArgs &a, const Seg &g, int lane)
+{
+    const int gl = lane & (LPF - 1), gbase = lane - gl;
+    const uint32_t L = g.lw & 0xFFFFu;  // > 10
+    const uint32_t NC = 4u * ((kHdr + L + 63u) >> 6);
+    const Span p = span_of(g);
+    uint8_t *dst = a.frames + (size_t)g.off * 64u;
+    auto load = [&](uint32_t c) -> uint4 {
+        const int64_t o = p.base + 16ll * ((int64_t)c - 3);
+        return ld16(a.payload + (o < p.lo ? p.lo : o > p.hi ? p.hi : o));
+    };
+    const int from = gl == LPF - 1 ? gbase : lane + 1;
+    uint32_t t[4] = {0u, 0u, 0u, 0u};
+    uint4 first = make_uint4(0u, 0u, 0u, 0u);
+    uint4 cur = load((uint32_t)gl);
+    for (uint32_t c0 = 0; c0 < NC; c0 += (uint32_t)LPF) {
+        const uint32_t c = c0 + (uint32_t)gl;
+        const uint4 nxt = load(c + (uint32_t)LPF);
+        // the source chunk after this lane's: the next lane's, or for the group's last lane
+        // the first lane's next
+        const uint4 put = gl == 0 ? nxt : cur;
+        uint4 N;
+        N.x = lane_read(put.x, from);
+        N.y = lane_read(put.y, from);
+        N.z = lane_read(put.z, from);
+        N.w = lane_read(put.w, from);
+        uint4 o = payload_chunk(cur, N, p.sh, c, L);
+        if (c < 3u) o = make_uint4(0u, 0u, 0u, 0u);
+        t[0] = dsum(o.x, t[0]);
+        t[1] = dsum(o.y, t[1]);
+        t[2] = dsum(o.z, t[2]);
+        t[3] = dsum(o.w, t[3]);
+        if (c < 4u) first = o;
+        else if (c < NC) st16(dst + 16u * c, o);
+        cur = nxt;
+    }
+    const uint32_t pay = lane_read(group_sum<LPF>(t[0] + t[1] + t[2] + t[3], lane), gbase);
+    if (gl < 4) st16(dst + 16u * (uint32_t)gl, header_chunk(g, (uint32_t)gl, pay, first));
+}
+
+// Lanes per frame of a segment: 0 = frame_small, else frame_stream<LPF>.
+__device__ __forceinline__ int class_of(uint32_t L)
+{
+    const uint32_t nc = 4u * ((kHdr + L + 63u) >> 6);
+    return nc <= 4u ? 0 : nc <= 16u ? 4 : nc <= 32u ? 8 : nc <= 64u ? 16 : nc <= 128u ? 32 : 64;
+}
+
+// The slice's segments of class CLS (lanes with cls == CLS), 64 / LPF per round.
+template <int CLS>
+__device__ __forceinline__ void run_class(const TbArgs &a, int cls, const Seg &mine, int lane_in)
+{
+    constexpr int LPF = CLS ? CLS : 4;
+    constexpr uint32_t FPW = 64 / LPF;
+    const unsigned long long m = __ballot(cls == CLS);
+    if (m == 0ull) return;
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));  // per-class lane math stays inside the class (VGPRs)
+    const uint32_t cnt = (uint32_t)__popcll(m);
+    // this class's lanes compacted to 0..cnt-1, keeping their order
+    uint32_t corig = (uint32_t)lane;
+    if (m != ~0ull) {
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t to = (cls == CLS) ? below : cnt + ((uint32_t)lane - below);
+        corig = (uint32_t)__builtin_amdgcn_ds_permute((int)(to << 2), lane);
+    }
+    for (uint32_t r = 0; r < cnt; r += FPW) {
+        const uint32_t k = r + (uint32_t)(lane / LPF);
+        const int src = (int)lane_read(corig, (int)(k & 63u));
+        Seg g;
+        g.s_lo = lane_read(mine.s_lo, src);
+        g.s_hi = lane_read(mine.s_hi, src);
+        g.lw = lane_read(mine.lw, src);
+        g.seq = lane_read(mine.seq, src);
+        g.ack = lane_read(mine.ack, src);
+        g.idf = lane_read(mine.idf, src);
+        g.off = lane_read(mine.off, src);
+        g.ports = lane_read(mine.ports, src);
+        g.ip_src_raw = lane_read(mine.ip_src_raw, src);
+        g.ip_dst_host = lane_read(mine.ip_dst_host, src);
+        g.m0 = lane_read(mine.m0, src);
+        g.m1 = lane_read(mine.m1, src);
+        g.m2 = lane_read(mine.m2, src);
+        if (k < cnt) {  // uniform over the group
+            if constexpr (CLS == 0) frame_small(a, g, lane);
+            else frame_stream<LPF>(a, g, lane);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void tx_build_kernel(TbArgs a)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), nwaves = gridDim.x * 4u;
+    uint32_t built = 0, skipped = 0;
+    for (uint32_t s = wave; s < a.nslices; s += nwaves) {
+        const uint32_t i = s * 64u + (uint32_t)lane;
+        const bool inb = i < a.n;
+        Seg g = {};
+        uint32_t flow = 0;
+        if (inb) {  // (8-byte loads: rxg_tx_seg needs 8-byte alignment only)
+            const uint2 *d = reinterpret_cast<const uint2 *>(a.segs + i);
+            const uint2 d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+            g.s_lo = d0.x; g.s_hi = d0.y;
+            flow = d1.x; g.seq = d1.y;
+            g.ack = d2.x; g.lw = d2.y;
+            g.idf = d3.x & 0x00FFFFFFu;
+        }
+        const uint64_t so = ((uint64_t)g.s_hi << 32) | g.s_lo;
+        const uint32_t L = g.lw & 0xFFFFu;
+        const bool valid = inb && flow < a.nflows && L <= RXG_TX_MAX_DATA && so <= a.payload_bytes &&
+                           (uint64_t)L <= a.payload_bytes - so;
+        if (valid) {
+            const uint2 *f = reinterpret_cast<const uint2 *>(a.flows + flow);
+            const uint2 f0 = f[0], f1 = f[1], f2 = f[2];
+            g.ports = f0.x; g.ip_src_raw = f0.y;
+            g.ip_dst_host = f1.x; g.m0 = f1.y;
+            g.m1 = f2.x; g.m2 = f2.y;
+            g.off = a.off64 ? a.off64[i] : a.slot0 + i * a.stride64;
+        }
+        if (inb) a.len[i] = valid ? (uint16_t)(kHdr + L) : (uint16_t)0;
+        built += (uint32_t)__popcll(__ballot(valid));
+        skipped += (uint32_t)__popcll(__ballot(inb && !valid));
+        const int cls = valid ? class_of(L) : -1;
+        run_class<0>(a, cls, g, lane);
+        run_class<4>(a, cls, g, lane);
+        run_class<8>(a, cls, g, lane);
+        run_class<16>(a, cls, g, lane);
+        run_class<32>(a, cls, g, lane);
+        run_class<64>(a, cls, g, lane);
+    }
+    // one atomic instruction per wave: lane 0 adds the built count, lane 1 the skipped
+    if (a.stats && lane < 2 && (built | skipped) != 0u)
+        atomicAdd(a.stats + lane, (unsigned long long)(lane == 0 ? built : skipped));
+}
+
+}  // namespace
+
+int tx_build_blocks_per_cu()
+{
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, tx_build_kernel, 256, 0);
+    return (e == hipSuccess && n > 0) ? n : 4;
+}
+
+hipError_t launch_tx_build(const LaunchTxBuild &B, hipStream_t st)
+{
+    if (B.n == 0) return hipSuccess;
+    TbArgs a;
+    a.payload = B.payload;
+    a.payload_bytes = B.payload_bytes;
+    a.flows = B.flows;
+    a.segs = B.segs;
+    a.frames = B.frames;
+    a.off64 = B.off64;
+    a.len = B.len;
+    a.stats = B.stats;
+    a.nflows = B.nflows;
+    a.n = B.n;
+    a.slot0 = B.slot0;
+    a.stride64 = B.stride64;
+    a.nslices = (uint32_t)(((uint64_t)B.n + 63u) / 64u);
+    uint32_t blocks = (a.nslices + 3u) / 4u;
+    if (B.max_blocks && blocks > B.max_blocks) blocks = B.max_blocks;
+    hipLaunchKernelGGL(tx_build_kernel, dim3(blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace rxg

@@ -87,6 +87,17 @@ TCB_DTYPE = np.dtype([("dport", "<i4"), ("sport", "<i4"), ("ipv4_dst", "<u4"),
                       ("identifier", "<u2")])
 assert REC16_DTYPE.itemsize == 16 and REC48_DTYPE.itemsize == 48 and TCB_DTYPE.itemsize == 20
 REC8_DTYPE = np.dtype([("w0", "<u4"), ("w1", "<u4")])
+# transmit segment build (rxg_tx_build_dev): rxg_tx_flow, rxg_tx_seg, rxg_tx_send
+TX_MAX_DATA = 65481
+REF_SRC_MAC = bytes([0x6A, 0x9C, 0xBA, 0xA0, 0x96, 0x24])  # etherout.c:94-99
+TX_FLOW_DTYPE = np.dtype([("dport", "<u2"), ("sport", "<u2"), ("ipv4_dst", "<u4"), ("ipv4_src", "<u4"),
+                          ("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("reserved", "u1", (8,))])
+TX_SEG_DTYPE = np.dtype([("src_off", "<u8"), ("flow", "<u4"), ("seq", "<u4"), ("ack", "<u4"),
+                         ("data_len", "<u2"), ("win_raw", "<u2"), ("ip_id", "<u2"), ("tcp_flags", "u1"),
+                         ("pad", "u1"), ("reserved", "<u4")])
+TX_SEND_DTYPE = np.dtype([("flow", "<u4"), ("next_seq", "<u4"), ("ack", "<u4"), ("src_off", "<u8"),
+                          ("bytes", "<u4"), ("tcp_flags", "u1"), ("pad", "u1", (3,)), ("win_raw", "<u2"),
+                          ("ip_id0", "<u2")], align=True)
 
 
 def rec8_pack(r16: np.ndarray) -> np.ndarray:
@@ -179,6 +190,34 @@ class DevStridedBurst(C.Structure):
 class DevTxBatch(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p),
                 ("n", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class TxFlow(C.Structure):
+    """rxg_tx_flow (TX_FLOW_DTYPE)."""
+    _fields_ = [("dport", C.c_uint16), ("sport", C.c_uint16), ("ipv4_dst", C.c_uint32), ("ipv4_src", C.c_uint32),
+                ("dst_mac", C.c_uint8 * 6), ("src_mac", C.c_uint8 * 6), ("reserved", C.c_uint8 * 8)]
+
+
+class TxSeg(C.Structure):
+    """rxg_tx_seg (TX_SEG_DTYPE)."""
+    _fields_ = [("src_off", C.c_uint64), ("flow", C.c_uint32), ("seq", C.c_uint32), ("ack", C.c_uint32),
+                ("data_len", C.c_uint16), ("win_raw", C.c_uint16), ("ip_id", C.c_uint16), ("tcp_flags", C.c_uint8),
+                ("pad", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+class TxSend(C.Structure):
+    """rxg_tx_send (TX_SEND_DTYPE): one send for rxg_tx_plan."""
+    _fields_ = [("flow", C.c_uint32), ("next_seq", C.c_uint32), ("ack", C.c_uint32), ("src_off", C.c_uint64),
+                ("bytes", C.c_uint32), ("tcp_flags", C.c_uint8), ("pad", C.c_uint8 * 3), ("win_raw", C.c_uint16),
+                ("ip_id0", C.c_uint16)]
+
+
+class DevTxBuild(C.Structure):
+    """rxg_dev_tx_build."""
+    _fields_ = [("payload", C.c_void_p), ("payload_bytes", C.c_uint64), ("flows", C.c_void_p),
+                ("nflows", C.c_uint32), ("n", C.c_uint32), ("segs", C.c_void_p), ("frames", C.c_void_p),
+                ("off64", C.c_void_p), ("slot0", C.c_uint32), ("stride64", C.c_uint32), ("len", C.c_void_p),
+                ("stats", C.c_void_p)]
 
 
 class PktView(C.Structure):
@@ -286,6 +325,8 @@ def load_library(path: str = LIB_PATH):
         "rxg_rx_bursts_strided_dev": (C.c_int, [vp, vp, u32, vp, u32, u32, vp]),
         "rxg_rx_burst": (C.c_int, [vp, C.POINTER(PktView), u32, u32, vp]),
         "rxg_tx_cksum_dev": (C.c_int, [vp, C.POINTER(DevTxBatch), vp]),
+        "rxg_tx_build_dev": (C.c_int, [vp, C.POINTER(DevTxBuild), vp]),
+        "rxg_tx_plan": (C.c_int64, [vp, u32, u32, vp, u64, vp]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -417,6 +458,29 @@ def ip_raw(a: int, b: int, c: int, d: int) -> int:
 
 def ip_host(a: int, b: int, c: int, d: int) -> int:
     return (a << 24) | (b << 16) | (c << 8) | d
+
+
+def tx_plan(sends, mss: int):
+    """rxg_tx_plan: sends (TX_SEND_DTYPE, or rows (flow, next_seq, ack, src_off, bytes, tcp_flags,
+    win_raw, ip_id0)) cut into segments of at most mss bytes.  Returns (segs TX_SEG_DTYPE,
+    next_seq u32 per send)."""
+    lib = load_library()
+    if not isinstance(sends, np.ndarray):
+        rows = list(sends)
+        sends = np.zeros(len(rows), dtype=TX_SEND_DTYPE)
+        for i, r in enumerate(rows):
+            for k, v in zip(("flow", "next_seq", "ack", "src_off", "bytes", "tcp_flags", "win_raw", "ip_id0"), r):
+                sends[i][k] = v
+    sends = np.ascontiguousarray(sends, dtype=TX_SEND_DTYPE)
+    if not 0 < mss <= TX_MAX_DATA:
+        raise RxgError(f"rxg_tx_plan failed (-22): mss {mss}")
+    cap = int(sum(max(1, -(-int(b) // mss)) for b in sends["bytes"]))
+    segs = np.zeros(cap, dtype=TX_SEG_DTYPE)
+    nxt = np.zeros(len(sends), dtype=np.uint32)
+    rc = lib.rxg_tx_plan(_ptr(sends), len(sends), mss, _ptr(segs), cap, _ptr(nxt))
+    if rc != cap:
+        raise RxgError(f"rxg_tx_plan failed ({rc})")
+    return segs, nxt
 
 
 # -------------------------------------------------------------------------- engine ---
@@ -682,6 +746,49 @@ class Engine:
     def tx_cksum_dev(self, frames: int, off64: int, lens: int, n: int, stream=None):
         b = DevTxBatch(frames, off64, lens, n, 0)
         _check(_lib.rxg_tx_cksum_dev(self.ctx, C.byref(b), stream), "rxg_tx_cksum_dev")
+
+    def tx_build_dev(self, payload: int, payload_bytes: int, flows: int, nflows: int, segs: int, n: int,
+                     frames: int, lens: int, off64: int | None = None, slot0: int = 0, stride64: int = 0,
+                     stats: int | None = None, stream=None):
+        """rxg_tx_build_dev: n segments (rxg_tx_seg at `segs`) built into the frame pool, at
+        off64[i] or at slot0 + i * stride64."""
+        b = DevTxBuild(payload, payload_bytes, flows, nflows, n, segs, frames, off64, slot0, stride64, lens, stats)
+        _check(_lib.rxg_tx_build_dev(self.ctx, C.byref(b), stream), "rxg_tx_build_dev")
+
+    def tx_build(self, payload: np.ndarray, flows: np.ndarray, segs: np.ndarray, off64=None, slot0: int = 0,
+                 stride64: int = 0):
+        """Upload the inputs, build the segments, sync.  Returns (arena u8, lens u16, stats u64[2]
+        = built, skipped); the arena covers the slots the call may write (frames of up to
+        ceil((54 + max data_len) / 64) slots), like tx_arena's."""
+        segs = np.ascontiguousarray(segs, dtype=TX_SEG_DTYPE)
+        flows = np.ascontiguousarray(flows, dtype=TX_FLOW_DTYPE)
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        n = len(segs)
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(0, np.uint16), np.zeros(2, np.uint64)
+        ok = segs["data_len"] <= TX_MAX_DATA
+        span = (54 + int(segs["data_len"][ok].max() if ok.any() else 0) + 63) // 64
+        if off64 is not None:
+            off64 = np.ascontiguousarray(off64, dtype=np.uint32)
+            slots = int(off64.max()) + span
+        else:
+            slots = slot0 + (n - 1) * stride64 + span
+        padded = np.zeros((payload.size + 15) // 16 * 16 or 16, np.uint8)
+        padded[:payload.size] = payload
+        dp, df, ds = self.to_device(padded), self.to_device(flows), self.to_device(segs)
+        do = self.to_device(off64) if off64 is not None else None
+        da, dl, dst = self.alloc(slots * 64), self.alloc(n * 2), self.alloc(16)
+        try:
+            _check(_lib.rxg_memset_dev(self.ctx, da.ptr, 0, slots * 64, None), "rxg_memset_dev")
+            _check(_lib.rxg_memset_dev(self.ctx, dst.ptr, 0, 16, None), "rxg_memset_dev")
+            self.tx_build_dev(dp.ptr, payload.size, df.ptr, len(flows), ds.ptr, n, da.ptr, dl.ptr,
+                              do.ptr if do else None, slot0, stride64, dst.ptr)
+            self.sync()
+            return da.download(np.uint8, slots * 64), dl.download(np.uint16, n), dst.download(np.uint64, 2)
+        finally:
+            for d in (dp, df, ds, do, da, dl, dst):
+                if d is not None:
+                    d.free()
 
     def rx_arena(self, arena: np.ndarray, off64: np.ndarray, lens: np.ndarray,
                  rec_kind: int = REC48) -> np.ndarray:

@@ -474,6 +474,101 @@ typedef struct rxg_dev_tx_batch {
 int rxg_tx_cksum_dev(rxg_ctx *ctx, const rxg_dev_tx_batch *b, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Transmit segment build: what sendtcpdata -> ip_out -> ether_out do per      */
+/* segment (tcp_out.c:157-207, ip.c:86-118, etherout.c:87-99) for a batch of   */
+/* segment descriptors, in one pass: the payload is read once from device      */
+/* memory, each frame is written once with its Ethernet, IPv4 and TCP headers  */
+/* and both checksums in place.                                                */
+/*                                                                             */
+/* Frame i is written at frames + 64 * off64[i] (off64 NULL: at frames + 64 *  */
+/* (slot0 + i * stride64)) as 54 header bytes, data_len payload bytes and      */
+/* zeros up to the next 64-byte boundary; nothing past that boundary is        */
+/* written.  Header fields:                                                    */
+/*   Ethernet  dst_mac, src_mac, 08 00                                         */
+/*   IPv4      version_ihl 0x45, total_length htons(40 + data_len), packet_id  */
+/*             ip_id as it stands (ip.c:106), ttl 127, proto 6, src_addr       */
+/*             ipv4_dst as it stands, dst_addr htonl(ipv4_src), hdr_checksum   */
+/*             as ip.c:107.  tos and fragment_offset are 0: the reference      */
+/*             leaves them as whatever the fresh mbuf held, rxg defines them.  */
+/*   TCP       src_port htons(dport), dst_port htons(sport), seq and ack       */
+/*             htonl, data_off 0x50 (20 bytes, no options: what sendtcpdata,   */
+/*             sendsyn, sendfin and send_reset build), tcp_flags, rx_win       */
+/*             win_raw as it stands, urp 0, cksum as ip.c:109-118 over         */
+/*             pseudo || header || payload (an odd last byte padded with 0).   */
+/* The kernel reads only 16-byte aligned chunks that overlap [src_off,         */
+/* src_off + data_len): the payload allocation is a multiple of 16 bytes.      */
+/*                                                                             */
+/* A segment with flow >= nflows, data_len > RXG_TX_MAX_DATA or src_off +      */
+/* data_len > payload_bytes is skipped: len[i] = 0, nothing written to its     */
+/* frame, stats[1] counts it; its flow index and offset are never followed.    */
+/* -EINVAL: a NULL argument, frames not 64-byte aligned, payload not 16-, segs */
+/* / flows / stats not 8-, off64 not 4-, len not 2-byte aligned, stride64 0 or */
+/* slot0 + (n - 1) * stride64 over 2^32 - 1 in strided mode.  n == 0 does      */
+/* nothing.                                                                    */
+/* Asynchronous on `stream`, as rxg_tx_cksum_dev; the TCB and ARP mirrors are  */
+/* neither read nor written.                                                   */
+/* ------------------------------------------------------------------------- */
+#define RXG_TX_MAX_DATA 65481u /* 54 + data_len fits the 16-bit frame length */
+#define RXG_REF_SRC_MAC {0x6a, 0x9c, 0xba, 0xa0, 0x96, 0x24} /* etherout.c:94-99 */
+
+typedef struct rxg_tx_flow { /* 32 bytes; the TCB fields sendtcpdata / ip_out read */
+    uint16_t dport, sport;   /* as in rxg_tcb_tuple (host order)                          */
+    uint32_t ipv4_dst;       /* raw network order, becomes ip src_addr (ip.c:97)          */
+    uint32_t ipv4_src;       /* host order, htonl() of it becomes ip dst_addr (ip.c:99)   */
+    uint8_t dst_mac[6];      /* what get_mac() returns for ipv4_src (etherout.c:176)      */
+    uint8_t src_mac[6];
+    uint8_t reserved[8];
+} rxg_tx_flow;
+
+typedef struct rxg_tx_seg { /* 32 bytes */
+    uint64_t src_off;       /* byte offset of the payload in `payload`, any alignment     */
+    uint32_t flow;          /* index into flows[]                                         */
+    uint32_t seq, ack;      /* host order; stored htonl (tcp_out.c:176,187)               */
+    uint16_t data_len;      /* 0 .. RXG_TX_MAX_DATA                                       */
+    uint16_t win_raw;       /* stored without a byte swap, as tcp_out.c:190,310 do        */
+    uint16_t ip_id;         /* stored without a byte swap, as ip.c:106 does               */
+    uint8_t tcp_flags;
+    uint8_t pad;
+    uint32_t reserved;
+} rxg_tx_seg;
+
+typedef struct rxg_dev_tx_build {
+    const void *payload;      /* dev, 16-byte aligned base */
+    uint64_t payload_bytes;
+    const rxg_tx_flow *flows; /* dev */
+    uint32_t nflows;
+    uint32_t n;
+    const rxg_tx_seg *segs;   /* dev, n entries */
+    void *frames;             /* dev, 64-byte aligned */
+    const uint32_t *off64;    /* dev, n entries; NULL = fixed stride */
+    uint32_t slot0, stride64; /* used when off64 == NULL */
+    uint16_t *len;            /* dev, n entries, written: 54 + data_len, 0 = skipped */
+    uint64_t *stats;          /* dev, 2 words, added to: {built, skipped}; may be NULL */
+} rxg_dev_tx_build;
+int rxg_tx_build_dev(rxg_ctx *ctx, const rxg_dev_tx_build *b, void *stream);
+
+/* Host-side planner (no context, no GPU): cuts each send into ceil(bytes / mss) segments
+   (bytes 0: one segment without data).  Sequence numbers advance as tcp_out.c:176-185:
+   + data_len per segment, + 1 for a segment carrying SYN, + 1 for one carrying FIN.  SYN goes
+   on a send's first segment only, FIN and PSH on its last only, every other flag on all.
+   ip_id counts up from ip_id0 (16-bit wrap).  Returns the number of segments written to out,
+   -ENOSPC if cap is too small (nothing past cap is written), -EINVAL for mss 0 or over
+   RXG_TX_MAX_DATA or a NULL sends / out.  next_seq_out[j] (may be NULL): the sequence number
+   after send j. */
+typedef struct rxg_tx_send {
+    uint32_t flow;
+    uint32_t next_seq, ack;
+    uint64_t src_off;
+    uint32_t bytes;
+    uint8_t tcp_flags;
+    uint8_t pad[3];
+    uint16_t win_raw;
+    uint16_t ip_id0;
+} rxg_tx_send;
+int64_t rxg_tx_plan(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss, rxg_tx_seg *out, uint64_t cap,
+                    uint32_t *next_seq_out);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
