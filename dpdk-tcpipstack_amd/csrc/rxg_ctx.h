@@ -85,6 +85,7 @@ struct rxg_ctx {
     uint32_t max_blocks = 0;        // rxg_config.max_blocks: grid cap (0 = occupancy grid)
     uint32_t grid_pay = 512;        // rxg_rx_burst_payload_dev's grid (set at init)
     uint32_t grid_txb = 0;          // rxg_tx_build_dev's occupancy grid (set at init)
+    uint32_t grid_txr = 0;          // rxg_tx_reset_dev's (its build pass)
     // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
     uint32_t grid[2][4] = {};
     rxg::PackPool pack_pool;  // rxg_rx_burst's packing threads
@@ -159,6 +160,16 @@ struct rxg_ctx {
     bool pm_pending = false;  // h_pm not fetched yet for this gather
     hipEvent_t pm_ev = nullptr;
     int64_t replay_pos = -1;  // packet whose handlers rxg_rx_replay is running
+
+    // rxg_tx_reset_dev: the slice counts its three launches share, and the event that orders a
+    // call on another stream after the previous call's use of them (recorded after every call)
+    DevBuf d_rst_counts;
+    hipEvent_t rst_ev = nullptr;
+    // rxg_reset_attach: host copies of a call's resets and their packet indices for the replay
+    // that follows (cleared when it returns), and rxg_reset_take's cursor into them
+    uint8_t *rst_host = nullptr;
+    const uint32_t *rst_idx = nullptr;
+    uint64_t rst_n = 0, rst_cur = 0;
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;

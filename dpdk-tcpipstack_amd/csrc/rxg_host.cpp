@@ -84,6 +84,7 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         // against 177)
         c->grid_pay = cus * 2u;
         c->grid_txb = cus * (uint32_t)tx_build_blocks_per_cu();  // rxg_tx_build_dev's occupancy grid
+        c->grid_txr = cus * (uint32_t)tx_reset_blocks_per_cu();  // rxg_tx_reset_dev's
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -162,8 +163,9 @@ extern "C" int rxg_fini(rxg_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->tables.wait_readers(true);  // table readers still running on caller streams
     for (DevBuf *b : {&c->tables.buckets, &c->tables.listen, &c->d_sel, &c->d_fix, &c->tables.d_arp, &c->d_pg_status,
-                      &c->d_pg_ticket, &c->d_soff})
+                      &c->d_pg_ticket, &c->d_soff, &c->d_rst_counts})
         if (b->p) (void)hipFree(b->p);
+    if (c->rst_ev) (void)hipEventDestroy(c->rst_ev);
     if (c->h_pm) (void)hipHostFree(c->h_pm);
     if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
     c->tables.destroy();
@@ -733,6 +735,63 @@ extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *str
     L.stats = (unsigned long long *)b->stats;
     L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txb ? c->grid_txb : 1024u);  // (as grid_for)
     HIP_OK(launch_tx_build(L, pick(c, stream)));
+    return 0;
+}
+
+static_assert(sizeof(rxg_dev_tx_reset) == 88, "reset build layout");
+
+extern "C" int rxg_tx_reset_dev(rxg_ctx *c, const rxg_dev_tx_reset *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_tx_reset_dev: NULL argument");
+    if (!b->frames || !b->len || !b->recs || !b->out || !b->idx || !b->count)
+        return fail(-EINVAL, "rxg_tx_reset_dev: NULL device pointer");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_tx_reset_dev: rec_kind %u", b->rec_kind);
+    const uintptr_t rec_align = b->rec_kind == RXG_REC8 ? 8u : 16u;  // (as rxg_rx_burst_dev)
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 63u) || ((uintptr_t)b->idx & 3u) ||
+        ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->count & 7u) ||
+        ((uintptr_t)b->recs & (rec_align - 1u)))
+        return fail(-EINVAL, "rxg_tx_reset_dev: frames need 16-byte, out 64-byte, idx and off64 4-byte, len 2-byte, "
+                             "count 8-byte, recs %u-byte alignment", (unsigned)rec_align);
+    if (!b->off64) {
+        if (!b->stride64) return fail(-EINVAL, "rxg_tx_reset_dev: stride64 0");
+        if (b->n && (uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
+            return fail(-EINVAL, "rxg_tx_reset_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchTxReset L;
+    L.frames = (const uint8_t *)b->frames;
+    L.off64 = b->off64;
+    L.len = b->len;
+    L.slot0 = b->slot0;
+    L.stride64 = b->stride64;
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.out = (uint8_t *)b->out;
+    L.idx = b->idx;
+    L.cap = b->cap;
+    L.count = (unsigned long long *)b->count;
+    L.counts = nullptr;
+    L.ip_id0 = b->ip_id0;
+    std::memcpy(L.src_mac, b->src_mac, 6);
+    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txr ? c->grid_txr : 1024u);  // (as grid_for)
+    if (b->n) {
+        // One call at a time uses the context's slice counts: a call waits, on its stream, for
+        // the previous call's last launch (rst_ev); before the buffer is replaced for a larger
+        // n the host waits for that launch instead.
+        const size_t need = tx_reset_count_bytes(b->n);
+        if (c->rst_ev && c->d_rst_counts.bytes < need) HIP_OK(hipEventSynchronize(c->rst_ev));
+        if ((rc = ensure(c->d_rst_counts, need))) return rc;
+        if (c->rst_ev) HIP_OK(hipStreamWaitEvent(st, c->rst_ev, 0));
+        else HIP_OK(hipEventCreateWithFlags(&c->rst_ev, hipEventDisableTiming));
+        L.counts = (uint32_t *)c->d_rst_counts.p;
+    }
+    const hipError_t e = launch_tx_reset(L, st);
+    // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
+    if (b->n) HIP_OK(hipEventRecord(c->rst_ev, st));
+    HIP_OK(e);
     return 0;
 }
 

@@ -175,6 +175,28 @@ struct LaunchTxBuild {
 };
 hipError_t launch_tx_build(const LaunchTxBuild &B, hipStream_t st);
 int tx_build_blocks_per_cu();  // resident 256-thread workgroups per CU of its kernel
+// rxg_txreset.hip: reset replies from a burst's records (rxg_tx_reset_dev): a count pass, a
+// one-workgroup scan and a build pass on `st` (n == 0: *count = 0 only)
+struct LaunchTxReset {
+    const uint8_t *frames;
+    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
+    const uint16_t *len;
+    uint32_t slot0, stride64;
+    uint32_t n;
+    uint32_t rec_kind;
+    const uint8_t *recs;
+    uint8_t *out;
+    uint32_t *idx;
+    unsigned long long cap;
+    unsigned long long *count;
+    uint32_t *counts;       // tx_reset_count_bytes(n) bytes, shared by the three launches
+    uint32_t ip_id0;
+    uint8_t src_mac[6];
+    uint32_t max_blocks;    // grid cap of the count and build passes (grid-stride); 0 = none
+};
+hipError_t launch_tx_reset(const LaunchTxReset &R, hipStream_t st);
+size_t tx_reset_count_bytes(uint32_t n);  // the slice-count buffer a call of n frames needs
+int tx_reset_blocks_per_cu();  // resident 256-thread workgroups per CU of the build pass
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

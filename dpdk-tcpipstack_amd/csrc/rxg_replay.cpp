@@ -1,7 +1,8 @@
 // rxg_replay.cpp — the per-packet replay of a classified burst into the caller's handlers
 // (rxg_rx_replay: the reference's ether_in -> ip_in -> tcp_in order, re-classifying what a
 // handler's table write changed), the payload hand-off (rxg_payload_gather_dev, rxg_rcv_set,
-// rxg_payload_take) and the one-frame rxg_ether_in.
+// rxg_payload_take), the prebuilt resets' hand-out (rxg_reset_attach, rxg_reset_take) and the
+// one-frame rxg_ether_in.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -141,6 +142,35 @@ extern "C" int rxg_payload_take(rxg_ctx *c, int32_t idx, uint32_t seq, uint32_t 
     return 1;
 }
 
+// ------------------------------------------------------------------ prebuilt resets ---
+extern "C" int rxg_reset_attach(rxg_ctx *c, void *resets_host, const uint32_t *idx_host, uint64_t nbuilt)
+{
+    if (!c || (nbuilt && (!resets_host || !idx_host)))
+        return fail(-EINVAL, "rxg_reset_attach: NULL argument");
+    c->rst_host = nbuilt ? (uint8_t *)resets_host : nullptr;
+    c->rst_idx = nbuilt ? idx_host : nullptr;
+    c->rst_n = nbuilt;
+    c->rst_cur = 0;
+    return 0;
+}
+
+// idx_host ascends (resets come out in packet order) and the replay's position only grows:
+// one cursor, moved to the first entry at or after the packet being replayed.  An entry
+// passed over belongs to a frame that no longer wants its reset (re-classified to DISPATCH,
+// or dropped by the checksum verify).
+extern "C" int rxg_reset_take(rxg_ctx *c, uint16_t ip_id, void **frame_out)
+{
+    if (!c || !frame_out) return fail(-EINVAL, "rxg_reset_take: NULL argument");
+    const int64_t pos = c->replay_pos;
+    if (pos < 0 || !c->rst_host) return 0;
+    while (c->rst_cur < c->rst_n && (int64_t)c->rst_idx[c->rst_cur] < pos) ++c->rst_cur;
+    if (c->rst_cur >= c->rst_n || (int64_t)c->rst_idx[c->rst_cur] != pos) return 0;
+    uint8_t *f = c->rst_host + 64u * c->rst_cur;
+    if ((uint16_t)(f[18] | (f[19] << 8)) != ip_id) rxg_reset_set_id(f, ip_id);
+    *frame_out = f;
+    return 1;
+}
+
 // ------------------------------------------------------------------------- replay ---
 static inline bool rec_is_tcp(const rxg_rec16 &r)
 {
@@ -242,7 +272,20 @@ static constexpr uint32_t kHostReclassifyMax = 256;
 extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const *mbufs,
                              void *const *frames, const void *recs, uint32_t n, uint32_t stride)
 {
-    if (!c || !ops || (n && (!mbufs || !frames || !recs)))
+    if (!c) return fail(-EINVAL, "rxg_rx_replay: NULL argument");
+    // on every way out: no packet is being replayed, and the resets attached for this replay
+    // (rxg_reset_attach) are no longer named
+    struct PosGuard {
+        rxg_ctx *c;
+        ~PosGuard()
+        {
+            c->replay_pos = -1;
+            c->rst_host = nullptr;
+            c->rst_idx = nullptr;
+            c->rst_n = c->rst_cur = 0;
+        }
+    } pos_guard{c};
+    if (!ops || (n && (!mbufs || !frames || !recs)))
         return fail(-EINVAL, "rxg_rx_replay: NULL argument");
     if (!rec_kind_ok(stride)) return fail(-EINVAL, "rxg_rx_replay: stride %u", stride);
     if (n && c->last_n != n)
@@ -252,10 +295,6 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
     // the re-classify launches and the counter correction run on this context's device
     // (a group replays several contexts from one thread, rxg_group.cpp)
     if (int rc = set_device(c)) return rc;
-    struct PosGuard {
-        rxg_ctx *c;
-        ~PosGuard() { c->replay_pos = -1; }
-    } pos_guard{c};
     std::vector<rxg_rec16> &cur = c->rp_cur;
     cur.resize(n);
     if (stride == RXG_REC8)

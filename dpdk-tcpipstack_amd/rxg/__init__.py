@@ -8,6 +8,7 @@ The reference surface this mirrors (rajneshrat/dpdk-tcpipstack, tcp_ip_stack/):
   ether_in/ip_in/tcp_in/findtcb per packet    -> Engine.rx_burst_dev / Engine.rx_burst
   tcbs[] writes (alloc_tcb, remove_tcb, state) -> Engine.tcb_upsert / tcb_remove / tcb_set_state
   ip_out's two checksums (ip.c:97-118)        -> Engine.tx_cksum_dev
+  send_reset per offender (tcp_out.c:103-146) -> Engine.tx_reset_dev, reset_attach / reset_take
 """
 from __future__ import annotations
 
@@ -220,6 +221,17 @@ class DevTxBuild(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class DevTxReset(C.Structure):
+    """rxg_dev_tx_reset."""
+    _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
+                ("stride64", C.c_uint32), ("n", C.c_uint32), ("rec_kind", C.c_uint32), ("recs", C.c_void_p),
+                ("out", C.c_void_p), ("idx", C.c_void_p), ("cap", C.c_uint64), ("count", C.c_void_p),
+                ("ip_id0", C.c_uint16), ("src_mac", C.c_uint8 * 6)]
+
+
+TX_RESET = DevTxReset
+
+
 class PktView(C.Structure):
     _fields_ = [("buf_addr", C.c_void_p), ("data_off", C.c_uint16), ("data_len", C.c_uint16),
                 ("pad", C.c_uint32)]
@@ -327,6 +339,10 @@ def load_library(path: str = LIB_PATH):
         "rxg_tx_cksum_dev": (C.c_int, [vp, C.POINTER(DevTxBatch), vp]),
         "rxg_tx_build_dev": (C.c_int, [vp, C.POINTER(DevTxBuild), vp]),
         "rxg_tx_plan": (C.c_int64, [vp, u32, u32, vp, u64, vp]),
+        "rxg_tx_reset_dev": (C.c_int, [vp, C.POINTER(DevTxReset), vp]),
+        "rxg_reset_set_id": (None, [vp, C.c_uint16]),
+        "rxg_reset_attach": (C.c_int, [vp, vp, vp, u64]),
+        "rxg_reset_take": (C.c_int, [vp, C.c_uint16, C.POINTER(vp)]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -481,6 +497,22 @@ def tx_plan(sends, mss: int):
     if rc != cap:
         raise RxgError(f"rxg_tx_plan failed ({rc})")
     return segs, nxt
+
+
+def reset_set_id(frame64, ip_id: int) -> bytes:
+    """rxg_reset_set_id: the 64-byte reset with packet_id ip_id (stored raw) and its
+    hdr_checksum recomputed.  frame64: bytes, or a writable uint8 array changed in place."""
+    lib = load_library()
+    if isinstance(frame64, np.ndarray):
+        if frame64.dtype != np.uint8 or frame64.size < 64 or not frame64.flags["C_CONTIGUOUS"]:
+            raise ValueError("reset_set_id: a contiguous uint8 array of 64 bytes")
+        lib.rxg_reset_set_id(_ptr(frame64), ip_id & 0xFFFF)
+        return frame64[:64].tobytes()
+    if len(frame64) < 64:
+        raise ValueError("reset_set_id: 64 bytes")
+    buf = C.create_string_buffer(bytes(frame64), len(frame64))
+    lib.rxg_reset_set_id(C.addressof(buf), ip_id & 0xFFFF)
+    return buf.raw[:64]
 
 
 # -------------------------------------------------------------------------- engine ---
@@ -754,6 +786,29 @@ class Engine:
         off64[i] or at slot0 + i * stride64."""
         b = DevTxBuild(payload, payload_bytes, flows, nflows, n, segs, frames, off64, slot0, stride64, lens, stats)
         _check(_lib.rxg_tx_build_dev(self.ctx, C.byref(b), stream), "rxg_tx_build_dev")
+
+    def tx_reset_dev(self, frames: int, lens: int, n: int, recs: int, rec_kind: int, out: int, idx: int, cap: int,
+                     count: int, off64: int | None = None, slot0: int = 0, stride64: int = 0, ip_id0: int = 0,
+                     src_mac: bytes = REF_SRC_MAC, stream=None):
+        """rxg_tx_reset_dev: a 64-byte reset at out + 64 * k for the k-th frame whose record (the
+        burst's, at `recs`) has an RST verdict, idx[k] = its packet index, *count = how many the
+        burst needs; the frames at off64[i] or at slot0 + i * stride64."""
+        b = DevTxReset(frames, off64, lens, slot0, stride64, n, rec_kind, recs, out, idx, cap, count, ip_id0 & 0xFFFF,
+                       (C.c_uint8 * 6)(*bytes(src_mac)))
+        _check(_lib.rxg_tx_reset_dev(self.ctx, C.byref(b), stream), "rxg_tx_reset_dev")
+
+    def reset_attach(self, resets_host: int, idx_host: int, nbuilt: int):
+        """rxg_reset_attach: host copies (addresses) of a tx_reset_dev call's out and idx for the
+        next rx replay; the caller keeps them alive until that replay returns."""
+        _check(_lib.rxg_reset_attach(self.ctx, resets_host, idx_host, nbuilt), "rxg_reset_attach")
+
+    def reset_take(self, ip_id: int):
+        """Inside a replay's send_reset: the address of the prebuilt 64-byte reset of the packet
+        being replayed, carrying ip_id, or None (the stack builds its own)."""
+        p = C.c_void_p()
+        rc = _lib.rxg_reset_take(self.ctx, ip_id & 0xFFFF, C.byref(p))
+        _check(min(rc, 0), "rxg_reset_take")
+        return p.value if rc == 1 else None
 
     def tx_build(self, payload: np.ndarray, flows: np.ndarray, segs: np.ndarray, off64=None, slot0: int = 0,
                  stride64: int = 0):

@@ -569,6 +569,89 @@ int64_t rxg_tx_plan(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss, rxg
                     uint32_t *next_seq_out);
 
 /* ------------------------------------------------------------------------- */
+/* Reset replies built on the device from a burst's records: what send_reset   */
+/* -> ip_out -> ether_out do per offending packet (tcp_out.c:103-146,          */
+/* ip.c:62-132, etherout.c:87-99).  A reset is built for every frame i whose   */
+/* record has verdict RXG_V_RST_NOPCB or RXG_V_RST_LISTEN_NONSYN, in packet    */
+/* order: reset k belongs to the k-th such frame, is written at out + 64 * k   */
+/* and idx[k] = i.  Resets with k >= cap are not written; *count is set to the */
+/* number the burst needs (as arena_used for the payload gather).              */
+/*                                                                             */
+/* A reset is one 64-byte line, a pure function of the first 64 bytes of the   */
+/* offending frame "in" (bytes at and beyond len[i] read as zero, as the rx    */
+/* kernel reads RXG_F_TRUNC frames; fixed offsets 14 / 34 whatever the IHL,    */
+/* tcp_in.c:42-45), ip_id0 + k and src_mac:                                    */
+/*   0-5    in[6..12), the offender's source MAC (see below)                   */
+/*   6-11   src_mac;  12-13  08 00                                             */
+/*   14     0x45; 15 and 20-21 zero (rxg's definition, as rxg_tx_build_dev)    */
+/*   16-17  htons(40);  18-19  (uint16_t)(ip_id0 + k) as it stands (ip.c:106)  */
+/*   22, 23 ttl 127, proto 6;  24-25  hdr_checksum as ip.c:107                 */
+/*   26-29  in[30..34), the raw dst_addr;  30-33  in[26..30), the raw src_addr */
+/*   34-35  in[36..38);  36-37  in[34..36)        (tcp_out.c:127-128)          */
+/*   38-41  in[42..46), the offender's recv_ack;  42-45  0  (tcp_out.c:129-130)*/
+/*   46, 47 0x50, RXG_TCP_FLAG_RST;  48-49  12000 unswapped (E0 2E)            */
+/*   50-51  TCP checksum over pseudo || the 20 header bytes (ip.c:109-118)     */
+/*   52-63  0                                                                  */
+/* The destination MAC: ether_out takes it from get_mac(ntohl(dst_addr)), which */
+/* after ip_in's learn (ip.c:30-32) is the offender's source MAC whenever the  */
+/* address was learned from this frame or from one with the same MAC; that is  */
+/* what rxg writes.  A stack that must honour an older ARP entry overwrites    */
+/* bytes 0-5: no checksum covers them.                                         */
+/*                                                                             */
+/* frames / off64 / len / slot0 / stride64 follow rxg_dev_batch's readability  */
+/* rules and rxg_dev_tx_build's strided form; recs are the burst's n records   */
+/* as the burst wrote them.  The call is a pure function of its arguments: it  */
+/* reads and writes no mirror and does not depend on the last burst of the     */
+/* context.  Asynchronous on `stream`.  The context owns a small device buffer */
+/* of per-slice counts that all calls share: a call on another stream waits    */
+/* (on the device, through an event) for the previous call on this context.    */
+/* -EINVAL: a NULL ctx, b, frames, len, recs, out, idx or count; a bad         */
+/* rec_kind; frames not 16-byte or out not 64-byte aligned; idx or off64 not   */
+/* 4-, len not 2-, count not 8-byte aligned, recs not 8- (RXG_REC8) or 16-byte */
+/* aligned; stride64 0 or slot0 + (n - 1) * stride64 over 2^32 - 1 in strided  */
+/* mode.  n == 0 writes *count = 0 and nothing else.                           */
+/* A group's members are plain contexts for this call; groups have no          */
+/* rxg_reset_take of their own.                                                */
+/* ------------------------------------------------------------------------- */
+typedef struct rxg_dev_tx_reset {
+    const void *frames;       /* dev: the burst's frame pool (rxg_dev_batch readability rules)   */
+    const uint32_t *off64;    /* dev, n entries; NULL = fixed stride (slot0 + i * stride64)      */
+    const uint16_t *len;      /* dev, n entries                                                  */
+    uint32_t slot0, stride64; /* used when off64 == NULL                                         */
+    uint32_t n;
+    uint32_t rec_kind;        /* RXG_REC8 / RXG_REC16 / RXG_REC48                                */
+    const void *recs;         /* dev: the burst's n records, as the burst wrote them             */
+    void *out;                /* dev, 64-byte aligned: reset k is written at out + 64 * k        */
+    uint32_t *idx;            /* dev: idx[k] = packet index i of reset k                         */
+    uint64_t cap;             /* slots in out / entries in idx                                   */
+    uint64_t *count;          /* dev, 1 word, WRITTEN (not added to): resets the burst needs     */
+    uint16_t ip_id0;          /* reset k carries packet_id (uint16_t)(ip_id0 + k), stored raw    */
+    uint8_t src_mac[6];       /* Ethernet source (RXG_REF_SRC_MAC for the reference's)           */
+} rxg_dev_tx_reset;
+int rxg_tx_reset_dev(rxg_ctx *ctx, const rxg_dev_tx_reset *b, void *stream);
+
+/* Host helper (no context, no GPU): gives a built reset another packet_id.  Stores ip_id as
+   it stands at bytes 18-19 and recomputes hdr_checksum (bytes 24-25) over the 20 header bytes
+   as ip.c:44-59,107 do. */
+void rxg_reset_set_id(uint8_t *frame64, uint16_t ip_id);
+
+/* Using the prebuilt resets during the replay.  rxg_reset_attach names host copies of a
+   rxg_tx_reset_dev call's `out` and `idx` (nbuilt = min(count, cap) entries) for the burst
+   the next rxg_rx_replay call on this context replays; the attachment ends when that replay
+   returns, however it returns.  rxg_reset_take is called from the stack's send_reset while
+   the replay runs a packet: if a reset was prebuilt for that packet it sets *frame_out to its
+   64-byte slot (given ip_id with rxg_reset_set_id if it was built with another: the stack's
+   count++ drifts whenever a handler sends something between two resets) and returns 1.
+   It returns 0 -- the stack runs its own send_reset -- for a packet that became a reset only
+   through re-classification, a reset past cap, a call outside a replay or with nothing
+   attached.  A prebuilt reset that is no longer wanted (the frame was re-classified to
+   RXG_V_DISPATCH) is passed over; a reset's bytes do not depend on the TCB mirror, so a
+   prebuilt one never goes stale.  -EINVAL: ctx or frame_out NULL (attach: ctx NULL, or a NULL
+   array with nbuilt != 0). */
+int rxg_reset_attach(rxg_ctx *ctx, void *resets_host, const uint32_t *idx_host, uint64_t nbuilt);
+int rxg_reset_take(rxg_ctx *ctx, uint16_t ip_id, void **frame_out);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
