@@ -250,3 +250,56 @@ def test_model_frames_verify_through_the_rx_oracle():
     assert (recs["c"]["tcb_idx"] == segs["flow"]).all()
     assert (recs["c"]["datalen"] == lens).all()
     assert (recs["seq"] == segs["seq"]).all() and (recs["ack"] == segs["ack"]).all()
+
+
+# --------------------------------------------------- the size classes of the test inputs ---
+def test_class_lengths_reach_every_class_at_both_ends():
+    """From the size-class rule alone (ref.lanes_per_frame, restated from the kernel's header
+    comment): CLASS_LENGTHS holds both ends of classes 0-32 and the lower end of class 64, and
+    every class whose frames can end inside a round has such a length."""
+    ends = {0: (0, 10), 4: (11, 202), 8: (203, 458), 16: (459, 970), 32: (971, 1994), 64: (1995, rxg.TX_MAX_DATA)}
+    assert ref.CLASS_RANGE == ends and list(ends) == ref.CLASSES
+    for cls, (lo, hi) in ends.items():
+        # the ends are ends: one byte less or more is another class
+        assert ref.lanes_per_frame(lo) == ref.lanes_per_frame(hi) == cls
+        assert lo == 0 or ref.lanes_per_frame(lo - 1) < cls
+        assert hi == rxg.TX_MAX_DATA or ref.lanes_per_frame(hi + 1) > cls
+        assert lo in ref.CLASS_LENGTHS
+        assert hi in ref.CLASS_LENGTHS or cls == 64
+    assert all(ref.lanes_per_frame(x) == 64 for x in (2731, 8960, 65481))
+    by_class = {c: [x for x in ref.CLASS_LENGTHS if ref.lanes_per_frame(x) == c] for c in ref.CLASSES}
+    assert all(by_class.values())
+    assert all(ref.chunks_of(x) == 4 * ((54 + x + 63) // 64) for x in ref.CLASS_LENGTHS)
+    # a partial last round: NC not a multiple of the lanes per frame.  Class 0 has one round
+    # of one line; NC is a multiple of 4 whatever the length, so class 4 has no partial round
+    # either: there, a length of several rounds and one of a single round
+    for cls in (8, 16, 32, 64):
+        assert any(ref.chunks_of(x) % cls for x in by_class[cls]), cls
+        assert any(x % 2 and ref.chunks_of(x) % cls for x in by_class[cls]), cls
+    assert {ref.chunks_of(x) for x in by_class[4]} >= {8, 16} and any(x % 2 for x in by_class[4])
+
+
+def test_model_class_lengths_verify_through_the_rx_oracle():
+    flows = ref.make_flows()
+    r = np.random.default_rng(13)
+    lens = np.array(ref.CLASS_LENGTHS)
+    payload = r.integers(0, 256, 8192, dtype=np.uint8)
+    segs = ref.make_segs(lens, r.integers(0, 8192 - 2731, len(lens)), len(flows), seed=14)
+    off, nslots = ref.packed_offsets(lens)
+    pool, flen, stats = ref.build(payload, flows, segs, off, nslots)
+    assert list(stats) == [len(lens), 0]
+    tcb = np.zeros(len(flows), dtype=rxg.TCB_DTYPE)
+    tcb["dport"], tcb["sport"] = flows["sport"], flows["dport"]
+    tcb["ipv4_dst"] = flows["ipv4_src"].byteswap()
+    tcb["ipv4_src"] = flows["ipv4_dst"].byteswap()
+    tcb["state"] = rxg.TCP_ESTABLISHED
+    recs, _ = oracle.rx_batch(pool, off, flen, tcb, np.ones(len(flows), np.uint8))
+    assert (recs["c"]["ip_cksum"] == 0).all() and (recs["c"]["tcp_cksum"] == 0).all()
+    assert (recs["c"]["verdict"] == rxg.V_DISPATCH).all()
+    assert (recs["c"]["tcb_idx"] == segs["flow"]).all()
+    assert (recs["c"]["datalen"] == lens).all()
+    assert (recs["seq"] == segs["seq"]).all() and (recs["ack"] == segs["ack"]).all()
+    # and the payload bytes are the source's
+    for i, L in enumerate(lens):
+        a, o = int(off[i]) * 64 + 54, int(segs["src_off"][i])
+        assert np.array_equal(pool[a:a + L], payload[o:o + L])

@@ -77,6 +77,33 @@ def build(payload, flows, segs, off64, nslots, fill=0):
 LENGTHS = [0, 1, 2, 9, 10, 11, 15, 16, 17, 63, 64, 65, 73, 74, 75, 999, 1000, 1459, 1460, 1461, 8960, 65481]
 
 
+def lanes_per_frame(L):
+    """The size class of a segment of data_len L, named by its lanes per frame, from the rule
+    in rxg_txbuild.hip's header comment: a frame of ceil((54 + L) / 64) lines; one line: class
+    0 (the one-line path), up to 4 / 8 / 16 / 32 lines: 4 / 8 / 16 / 32 lanes, more: 64."""
+    lines = -(-(HDR + int(L)) // 64)
+    for most, lanes in ((1, 0), (4, 4), (8, 8), (16, 16), (32, 32)):
+        if lines <= most:
+            return lanes
+    return 64
+
+
+def chunks_of(L):
+    """NC: the frame's 16-byte chunks, four per line."""
+    return 4 * -(-(HDR + int(L)) // 64)
+
+
+CLASSES = [0, 4, 8, 16, 32, 64]
+# class -> (smallest, largest) data_len, by the same rule: k lines hold 64 k - 54 payload bytes
+CLASS_RANGE = {0: (0, 10), 4: (11, 4 * 64 - HDR), 8: (4 * 64 - HDR + 1, 8 * 64 - HDR),
+               16: (8 * 64 - HDR + 1, 16 * 64 - HDR), 32: (16 * 64 - HDR + 1, 32 * 64 - HDR),
+               64: (32 * 64 - HDR + 1, rxg.TX_MAX_DATA)}
+# both ends of every class (class 64: its lower end), one odd length inside each streamed
+# class whose last round is partial where the class has one (139: NC 16 = 4 rounds of 4;
+# 331: NC 28; 715: NC 52; 1483: NC 100), and 2731 (NC 176), a class-64 length of 44 lines
+CLASS_LENGTHS = [0, 10, 11, 202, 203, 458, 459, 970, 971, 1994, 1995, 139, 331, 715, 1483, 2731]
+
+
 def make_flows(n=8, seed=7):
     """n flows with distinct MACs, addresses and ports."""
     r = np.random.default_rng(seed)
