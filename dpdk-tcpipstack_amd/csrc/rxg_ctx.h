@@ -85,6 +85,7 @@ struct rxg_ctx {
     uint32_t max_blocks = 0;        // rxg_config.max_blocks: grid cap (0 = occupancy grid)
     uint32_t grid_pay = 512;        // rxg_rx_burst_payload_dev's grid (set at init)
     uint32_t grid_txb = 0;          // rxg_tx_build_dev's occupancy grid (set at init)
+    uint32_t grid_txbo = 0;         // rxg_tx_build_opt_dev's
     uint32_t grid_txr = 0;          // rxg_tx_reset_dev's (its build pass)
     // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
     uint32_t grid[2][4] = {};

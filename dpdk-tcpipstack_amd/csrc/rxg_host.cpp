@@ -83,7 +83,8 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         // (8 waves) measured faster than the occupancy grid's 3 (C3 621 against 627 us, C4 174
         // against 177)
         c->grid_pay = cus * 2u;
-        c->grid_txb = cus * (uint32_t)tx_build_blocks_per_cu();  // rxg_tx_build_dev's occupancy grid
+        c->grid_txb = cus * (uint32_t)tx_build_blocks_per_cu(false);  // rxg_tx_build_dev's occupancy grid
+        c->grid_txbo = cus * (uint32_t)tx_build_blocks_per_cu(true);  // rxg_tx_build_opt_dev's
         c->grid_txr = cus * (uint32_t)tx_reset_blocks_per_cu();  // rxg_tx_reset_dev's
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
@@ -702,21 +703,27 @@ extern "C" int rxg_tx_cksum_dev(rxg_ctx *c, const rxg_dev_tx_batch *b, void *str
 static_assert(sizeof(rxg_tx_flow) == 32 && sizeof(rxg_tx_seg) == 32 && sizeof(rxg_dev_tx_build) == 80,
               "transmit segment build layouts");
 
-extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *stream)
+// rxg_tx_build_dev and rxg_tx_build_opt_dev (`opt`: its block table): one argument check, one launch
+static int tx_build_call(const char *who, rxg_ctx *c, const rxg_dev_tx_build *b, const rxg_dev_tx_build_opt *opt,
+                         void *stream)
 {
-    if (!c || !b) return fail(-EINVAL, "rxg_tx_build_dev: NULL argument");
+    if (!c || !b) return fail(-EINVAL, "%s: NULL argument", who);
     if (b->n == 0) return 0;
     if (!b->payload || !b->flows || !b->segs || !b->frames || !b->len)
-        return fail(-EINVAL, "rxg_tx_build_dev: NULL device pointer");
+        return fail(-EINVAL, "%s: NULL device pointer", who);
     if (((uintptr_t)b->payload & 15u) || ((uintptr_t)b->frames & 63u) || ((uintptr_t)b->segs & 7u) ||
         ((uintptr_t)b->flows & 7u) || ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) ||
         ((uintptr_t)b->stats & 7u))
-        return fail(-EINVAL, "rxg_tx_build_dev: payload needs 16-byte, frames 64-byte, segs, flows and stats "
-                             "8-byte, off64 4-byte, len 2-byte alignment");
+        return fail(-EINVAL, "%s: payload needs 16-byte, frames 64-byte, segs, flows and stats "
+                             "8-byte, off64 4-byte, len 2-byte alignment", who);
     if (!b->off64) {
-        if (!b->stride64) return fail(-EINVAL, "rxg_tx_build_dev: stride64 0");
+        if (!b->stride64) return fail(-EINVAL, "%s: stride64 0", who);
         if ((uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
-            return fail(-EINVAL, "rxg_tx_build_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
+            return fail(-EINVAL, "%s: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots", who);
+    }
+    if (opt) {
+        if ((uintptr_t)opt->opts & 15u) return fail(-EINVAL, "%s: opts needs 16-byte alignment", who);
+        if (!opt->opts && opt->nopts) return fail(-EINVAL, "%s: NULL opts with nopts %u", who, opt->nopts);
     }
     int rc = set_device(c);
     if (rc) return rc;
@@ -733,9 +740,25 @@ extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *str
     L.stride64 = b->stride64;
     L.len = b->len;
     L.stats = (unsigned long long *)b->stats;
-    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txb ? c->grid_txb : 1024u);  // (as grid_for)
+    const uint32_t grid = opt ? c->grid_txbo : c->grid_txb;
+    L.max_blocks = c->max_blocks ? c->max_blocks : (grid ? grid : 1024u);  // (as grid_for)
+    L.with_opts = opt != nullptr;
+    L.opts = opt ? opt->opts : nullptr;
+    L.nopts = opt ? opt->nopts : 0u;
     HIP_OK(launch_tx_build(L, pick(c, stream)));
     return 0;
+}
+
+extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *stream)
+{
+    return tx_build_call("rxg_tx_build_dev", c, b, nullptr, stream);
+}
+
+static_assert(sizeof(rxg_tx_opt) == 48 && sizeof(rxg_dev_tx_build_opt) == 96, "option build layouts");
+
+extern "C" int rxg_tx_build_opt_dev(rxg_ctx *c, const rxg_dev_tx_build_opt *b, void *stream)
+{
+    return tx_build_call("rxg_tx_build_opt_dev", c, b ? &b->b : nullptr, b, stream);
 }
 
 static_assert(sizeof(rxg_dev_tx_reset) == 88, "reset build layout");

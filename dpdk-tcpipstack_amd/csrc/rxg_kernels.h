@@ -158,7 +158,7 @@ hipError_t launch_server(const LaunchServer &L, hipStream_t st);
 // rxg_payload.hip: gather of the burst's candidate payloads (one launch + a memset)
 hipError_t launch_payload(const LaunchPayload &P, hipStream_t st, uint32_t *tickets_used);
 uint32_t payload_blocks(uint32_t n);
-// rxg_txbuild.hip: transmit segment build (rxg_tx_build_dev), one launch
+// rxg_txbuild.hip: transmit segment build (rxg_tx_build_dev, rxg_tx_build_opt_dev), one launch
 struct LaunchTxBuild {
     const uint8_t *payload;
     uint64_t payload_bytes;
@@ -172,9 +172,12 @@ struct LaunchTxBuild {
     uint16_t *len;
     unsigned long long *stats;  // {built, skipped}, added to; may be nullptr
     uint32_t max_blocks;        // grid cap (grid-stride over 64-segment slices); 0 = none
+    bool with_opts;             // rxg_tx_build_opt_dev: rxg_tx_seg.reserved names a block of opts
+    const rxg_tx_opt *opts;     // nopts blocks (16-byte aligned), or nullptr with nopts 0
+    uint32_t nopts;
 };
 hipError_t launch_tx_build(const LaunchTxBuild &B, hipStream_t st);
-int tx_build_blocks_per_cu();  // resident 256-thread workgroups per CU of its kernel
+int tx_build_blocks_per_cu(bool with_opts);  // resident 256-thread workgroups per CU of its kernel
 // rxg_txreset.hip: reset replies from a burst's records (rxg_tx_reset_dev): a count pass, a
 // one-workgroup scan and a build pass on `st` (n == 0: *count = 0 only)
 struct LaunchTxReset {

@@ -38,12 +38,30 @@
 //
 // Roofline: HBM, algorithmic bytes per segment = data_len (read) + 32 (descriptor) +
 // 64 * ceil((54 + data_len) / 64) (written) + 2 (len).
+//
+// rxg_tx_build_opt_dev is the same kernel instantiated with OPT = true: a segment may carry
+// O = 0, 4, .. 40 option bytes from a table of 48-byte blocks (rxg_tx_opt) between the TCP
+// header and its payload.  With H = 54 + O (even, so a chunk's 16-bit words stay the
+// checksum's words) everything above holds with H for 54: NC = 4 * ceil((H + L) / 64), which
+// also gives the size class (one line: H + L <= 64, O <= 8 only); chunk c >= 3 takes its
+// payload from the aligned source chunk at ((src_off + 48 - H) & ~15) + 16 * (c - 3) with
+// shift (src_off + 10 - O) mod 16, masked to frame bytes [H, H + L).  The option bytes never
+// travel between lanes: a block's three 16-byte chunks are the images of frame chunks 3, 4
+// and 5 (rxg.h), so the lane that owns one of those chunks loads it aligned (issued with the
+// lane's first payload load), masks it to frame bytes [54, H) and ORs it into the chunk
+// before the chunk is summed and stored.  For O >= 12 the second line begins with option
+// bytes and is stored in the stream like any other line.  A segment without data reads
+// nothing of the payload (a streamed frame can have L == 0 here: O >= 12).  The OPT = false
+// instantiation is the kernel as it was.  Algorithmic bytes: + 48 per distinct block, and
+// 64 * ceil((H + data_len) / 64) written.
+#include <type_traits>
+
 #include "rxg_kernels.h"
 
 namespace rxg {
 namespace {
 
-constexpr uint32_t kHdr = 54;  // Ethernet 14 + IPv4 20 + TCP 20 (data_off 0x50, no options)
+constexpr uint32_t kHdr = 54;  // Ethernet 14 + IPv4 20 + TCP 20 (data_off 0x50 without options)
 
 struct TbArgs {
     const uint8_t *payload;
@@ -57,12 +75,21 @@ struct TbArgs {
     uint32_t nflows, n, slot0, stride64, nslices;
 };
 
+struct TbArgsOpt : TbArgs {
+    const rxg_tx_opt *opts;
+    uint32_t nopts;
+};
+
+template <bool OPT>
+using Args = std::conditional_t<OPT, TbArgsOpt, TbArgs>;
+
 // A segment's descriptor and flow record as its lane (and, broadcast, its group) holds them.
 struct Seg {
     uint32_t s_lo, s_hi;  // src_off
     uint32_t lw;          // data_len | win_raw << 16
     uint32_t seq, ack;
-    uint32_t idf;         // ip_id | tcp_flags << 16
+    uint32_t idf;         // ip_id | tcp_flags << 16 (OPT: | O << 24, the option bytes)
+    uint32_t opt;         // OPT: rxg_tx_seg.reserved, the block's index + 1 (unused otherwise)
     uint32_t off;         // 64-byte slot of the frame
     uint32_t ports;       // dport | sport << 16
     uint32_t ip_src_raw;  // rxg_tx_flow.ipv4_dst: the frame's src_addr as stored
@@ -142,31 +169,98 @@ __device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
     return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
 }
 
+__device__ __forceinline__ uint32_t drop_bytes(uint32_t v, int nb)
+{
+    return nb >= 4 ? 0u : nb <= 0 ? v : (v & ~((1u << (8 * nb)) - 1u));
+}
+
+// The option bytes of a segment (OPT; 0 otherwise) and its headers' length.
+template <bool OPT>
+__device__ __forceinline__ uint32_t opt_len(const Seg &g)
+{
+    if constexpr (OPT) return g.idf >> 24;
+    else return 0u;
+}
+
+template <bool OPT>
+__device__ __forceinline__ uint32_t hdr_len(const Seg &g) { return kHdr + opt_len<OPT>(g); }
+
 // Frame chunk c >= 3 from the source chunks lo || hi: the payload bytes it holds, zero
-// elsewhere (frame bytes 48-53 of chunk 3, and bytes at or past 54 + L).
-__device__ __forceinline__ uint4 payload_chunk(uint4 lo, uint4 hi, uint32_t sh, uint32_t c, uint32_t L)
+// elsewhere (frame bytes before H = 54 + O: 48-53 of chunk 3 and the option bytes, and bytes
+// at or past H + L).
+template <bool OPT>
+__device__ __forceinline__ uint4 payload_chunk(uint4 lo, uint4 hi, uint32_t sh, uint32_t c, uint32_t L, uint32_t H)
 {
     uint4 o = sh ? funnel16(lo, hi, sh) : lo;
-    const int vb = (int)(kHdr + L) - (int)(16u * c);
+    const int vb = (int)(H + L) - (int)(16u * c);
     if (vb < 16) {
         o.x = keep_bytes(o.x, vb);
         o.y = keep_bytes(o.y, vb - 4);
         o.z = keep_bytes(o.z, vb - 8);
         o.w = keep_bytes(o.w, vb - 12);
     }
-    if (c == 3u) {
+    if constexpr (OPT) {
+        const int hb = (int)H - (int)(16u * c);  // > 0 in chunks 3, 4 (O >= 12) and 5 (O >= 28) only
+        if (hb > 0) {
+            o.x = drop_bytes(o.x, hb);
+            o.y = drop_bytes(o.y, hb - 4);
+            o.z = drop_bytes(o.z, hb - 8);
+            o.w = drop_bytes(o.w, hb - 12);
+        }
+    } else if (c == 3u) {
         o.x = 0u;
         o.y &= 0xFFFF0000u;
     }
     return o;
 }
 
+// The 16-byte chunk c - 3 of a segment's option block (the image of frame chunk c, c = 3, 4,
+// 5: rxg.h) masked to the option bytes, frame bytes [54, H).
+__device__ __forceinline__ uint4 option_chunk(uint4 v, uint32_t c, uint32_t H)
+{
+    const int hb = (int)H - (int)(16u * c);
+    v.x = keep_bytes(v.x, hb);
+    v.y = keep_bytes(v.y, hb - 4);
+    v.z = keep_bytes(v.z, hb - 8);
+    v.w = keep_bytes(v.w, hb - 12);
+    if (c == 3u) {
+        v.x = 0u;
+        v.y &= 0xFFFF0000u;
+    }
+    return v;
+}
+
+// Which chunk of its segment's block a lane of a group of LPF loads: that of the one frame
+// chunk among 3, 4, 5 the lane owns (LPF 4: lane 3 in round 0, lanes 0 and 1 in round 1),
+// 3 or more = none.
+template <int LPF>
+__device__ __forceinline__ uint32_t option_chunk_of(int gl)
+{
+    return LPF == 4 ? ((uint32_t)gl + 1u) & 3u : (uint32_t)gl - 3u;
+}
+
+// Chunk oc of block k - 1 if it holds option bytes of a block of O bytes (frame bytes 48 +
+// 16 oc up to 54 + O), else zeros and no load.  A plain load: segments share blocks.
+template <bool OPT>
+__device__ __forceinline__ uint4 load_option_chunk(const Args<OPT> &a, uint32_t k, uint32_t O, uint32_t oc)
+{
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (OPT) {
+        if (O != 0u && oc < 3u && 16u * oc < 6u + O)
+            v = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(a.opts + (k - 1u)) + 16u * oc);
+    }
+    return v;
+}
+
 // Chunk c < 4 of the frame's first line: the headers of etherout.c:87-99, ip.c:97-118 and
-// tcp_out.c:174-193 with both checksums, `pay` the payload sum of the whole segment (16-bit
-// little-endian words) and p3 chunk 3's payload part (payload_chunk).
+// tcp_out.c:174-193 with both checksums, `pay` the sum of the whole segment's option and
+// payload bytes (16-bit little-endian words) and p3 chunk 3's part of them (payload_chunk,
+// option_chunk).
+template <bool OPT>
 __device__ __forceinline__ uint4 header_chunk(const Seg &g, uint32_t c, uint32_t pay, uint4 p3)
 {
-    const uint32_t L = g.lw & 0xFFFFu, win = g.lw >> 16;
+    const uint32_t O = opt_len<OPT>(g);
+    const uint32_t L = (g.lw & 0xFFFFu) + O, win = g.lw >> 16;  // L: what follows the 20-byte TCP header
     const uint32_t ipid = g.idf & 0xFFFFu, flags = (g.idf >> 16) & 0xFFu;
     const uint32_t dst = bswap32(g.ip_dst_host), src = g.ip_src_raw;
     const uint32_t seq = bswap32(g.seq), ack = bswap32(g.ack);
@@ -179,8 +273,8 @@ __device__ __forceinline__ uint4 header_chunk(const Seg &g, uint32_t c, uint32_t
     // complement as it stands (htons(calculate_checksum(..)), ip.c:107,118)
     const uint32_t isum = 0x0045u + hsum(h4) + hsum(h5) + hsum(src) + hsum(dst);
     const uint32_t ipck = (~fold16(isum)) & 0xFFFFu;
-    const uint32_t h11 = (ack >> 16) | (0x50u << 16) | (flags << 24);
-    // pseudo {src, dst, 0, 6, htons(20 + L)} || TCP header (cksum, urp 0) || payload
+    const uint32_t h11 = (ack >> 16) | ((0x50u + (O << 2)) << 16) | (flags << 24);  // data_off (5 + O / 4) << 4
+    // pseudo {src, dst, 0, 6, htons(20 + L)} || TCP header (cksum, urp 0) || options || payload
     const uint32_t tsum = pay + hsum(src) + hsum(dst) + 0x0600u + bswap16((20u + L) & 0xFFFFu) + sp + dp +
                           hsum(seq) + hsum(ack) + (h11 >> 16) + win;
     const uint32_t tck = (~fold16(tsum)) & 0xFFFFu;
@@ -198,52 +292,76 @@ struct Span {
     uint32_t sh;
 };
 
+template <bool OPT>
 __device__ __forceinline__ Span span_of(const Seg &g)
 {
     const uint64_t s = ((uint64_t)g.s_hi << 32) | g.s_lo;
     const uint32_t L = g.lw & 0xFFFFu;
+    const uint32_t O = opt_len<OPT>(g);
     Span p;
-    p.base = ((int64_t)s - 6) & ~15ll;
+    p.base = ((int64_t)s - 6 - (int64_t)O) & ~15ll;
     p.lo = (int64_t)(s & ~15ull);
     p.hi = (int64_t)((s + L - 1u) & ~15ull);  // (L > 0)
-    p.sh = (uint32_t)(s + 10u) & 15u;
+    p.sh = (uint32_t)(s + 10u - O) & 15u;
     return p;
 }
 
-// A frame of one line (L <= 10), 4 lanes: lane 3 loads what the payload touches.
-__device__ __forceinline__ void frame_small(const TbArgs &a, const Seg &g, int lane)
+// A frame of one line (H + L <= 64: L <= 10 - O), 4 lanes: lane 3 loads what the payload
+// touches and, of a block of 4 or 8 bytes, its first chunk.
+template <bool OPT>
+__device__ __forceinline__ void frame_small(const Args<OPT> &a, const Seg &g, int lane)
 {
     const uint32_t c = (uint32_t)lane & 3u;
     const uint32_t L = g.lw & 0xFFFFu;
+    const uint32_t O = opt_len<OPT>(g);
     uint4 p3 = make_uint4(0u, 0u, 0u, 0u);
     uint32_t pay = 0;
     if (c == 3u && L != 0u) {
-        const Span p = span_of(g);
+        const Span p = span_of<OPT>(g);
         uint4 A = make_uint4(0u, 0u, 0u, 0u), N = A;
         if (p.base >= p.lo) A = ld16(a.payload + p.base);
         if (p.base + 16 >= p.lo && p.base + 16 <= p.hi) N = ld16(a.payload + p.base + 16);
-        p3 = payload_chunk(A, N, p.sh, 3u, L);
+        p3 = payload_chunk<OPT>(A, N, p.sh, 3u, L, kHdr + O);
         pay = hsum(p3.y) + hsum(p3.z) + hsum(p3.w);
     }
-    st16(a.frames + (size_t)g.off * 64u + 16u * c, header_chunk(g, c, pay, p3));
+    if constexpr (OPT) {
+        if (c == 3u && O != 0u) {
+            const uint4 q = option_chunk(load_option_chunk<OPT>(a, g.opt, O, 0u), 3u, kHdr + O);
+            p3.y |= q.y; p3.z |= q.z; p3.w |= q.w;
+            pay += hsum(q.y) + hsum(q.z) + hsum(q.w);
+        }
+    }
+    st16(a.frames + (size_t)g.off * 64u + 16u * c, header_chunk<OPT>(g, c, pay, p3));
 }
 
-template <int LPF>
-__device__ __forceinline__ void frame_stream(const TbArgs &a, const Seg &g, int lane)
+template <bool OPT, int LPF>
+__device__ __forceinline__ void frame_stream(const Args<OPT> &a, const Seg &g, int lane)
 {
     const int gl = lane & (LPF - 1), gbase = lane - gl;
-    const uint32_t L = g.lw & 0xFFFFu;  // > 10
-    const uint32_t NC = 4u * ((kHdr + L + 63u) >> 6);
-    const Span p = span_of(g);
+    const uint32_t L = g.lw & 0xFFFFu;  // > 10 (OPT: any, with H + L > 64)
+    const uint32_t H = hdr_len<OPT>(g);
+    const uint32_t NC = 4u * ((H + L + 63u) >> 6);
+    const Span p = span_of<OPT>(g);
     uint8_t *dst = a.frames + (size_t)g.off * 64u;
+    // OPT: the clamp as 32-bit offsets from p.base (lo - base <= 48, hi - base < 2^16 + 64)
+    const uint8_t *src = a.payload + p.base;
+    const int dlo = (int)(p.lo - p.base), dhi = (int)(p.hi - p.base);
     auto load = [&](uint32_t c) -> uint4 {
-        const int64_t o = p.base + 16ll * ((int64_t)c - 3);
-        return ld16(a.payload + (o < p.lo ? p.lo : o > p.hi ? p.hi : o));
+        if constexpr (OPT) {
+            if (L == 0u) return make_uint4(0u, 0u, 0u, 0u);  // a segment without data reads nothing of the payload
+            const int o = 16 * ((int)c - 3);
+            return ld16(src + (o < dlo ? dlo : o > dhi ? dhi : o));
+        } else {
+            const int64_t o = p.base + 16ll * ((int64_t)c - 3);
+            return ld16(a.payload + (o < p.lo ? p.lo : o > p.hi ? p.hi : o));
+        }
     };
     const int from = gl == LPF - 1 ? gbase : lane + 1;
     uint32_t t[4] = {0u, 0u, 0u, 0u};
     uint4 first = make_uint4(0u, 0u, 0u, 0u);
     uint4 cur = load((uint32_t)gl);
+    // OPT: this lane's chunk of the block, in flight with its first payload chunk
+    const uint4 ov = load_option_chunk<OPT>(a, g.opt, H - kHdr, option_chunk_of<LPF>(gl));
     for (uint32_t c0 = 0; c0 < NC; c0 += (uint32_t)LPF) {
         const uint32_t c = c0 + (uint32_t)gl;
         const uint4 nxt = load(c + (uint32_t)LPF);
@@ -255,8 +373,14 @@ __device__ __forceinline__ void frame_stream(const TbArgs &a, const Seg &g, int 
         N.y = lane_read(put.y, from);
         N.z = lane_read(put.z, from);
         N.w = lane_read(put.w, from);
-        uint4 o = payload_chunk(cur, N, p.sh, c, L);
+        uint4 o = payload_chunk<OPT>(cur, N, p.sh, c, L, H);
         if (c < 3u) o = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (OPT) {
+            if (c - 3u < 3u) {  // the one chunk of 3, 4, 5 this lane owns: ov is its image
+                const uint4 q = option_chunk(ov, c, H);
+                o.x |= q.x; o.y |= q.y; o.z |= q.z; o.w |= q.w;
+            }
+        }
         t[0] = dsum(o.x, t[0]);
         t[1] = dsum(o.y, t[1]);
         t[2] = dsum(o.z, t[2]);
@@ -266,19 +390,19 @@ __device__ __forceinline__ void frame_stream(const TbArgs &a, const Seg &g, int 
         cur = nxt;
     }
     const uint32_t pay = lane_read(group_sum<LPF>(t[0] + t[1] + t[2] + t[3], lane), gbase);
-    if (gl < 4) st16(dst + 16u * (uint32_t)gl, header_chunk(g, (uint32_t)gl, pay, first));
+    if (gl < 4) st16(dst + 16u * (uint32_t)gl, header_chunk<OPT>(g, (uint32_t)gl, pay, first));
 }
 
-// Lanes per frame of a segment: 0 = frame_small, else frame_stream<LPF>.
-__device__ __forceinline__ int class_of(uint32_t L)
+// Lanes per frame of a segment of HL = H + L bytes: 0 = frame_small, else frame_stream<LPF>.
+__device__ __forceinline__ int class_of(uint32_t HL)
 {
-    const uint32_t nc = 4u * ((kHdr + L + 63u) >> 6);
+    const uint32_t nc = 4u * ((HL + 63u) >> 6);
     return nc <= 4u ? 0 : nc <= 16u ? 4 : nc <= 32u ? 8 : nc <= 64u ? 16 : nc <= 128u ? 32 : 64;
 }
 
 // The slice's segments of class CLS (lanes with cls == CLS), 64 / LPF per round.
-template <int CLS>
-__device__ __forceinline__ void run_class(const TbArgs &a, int cls, const Seg &mine, int lane_in)
+template <bool OPT, int CLS>
+__device__ __forceinline__ void run_class(const Args<OPT> &a, int cls, const Seg &mine, int lane_in)
 {
     constexpr int LPF = CLS ? CLS : 4;
     constexpr uint32_t FPW = 64 / LPF;
@@ -311,14 +435,17 @@ __device__ __forceinline__ void run_class(const TbArgs &a, int cls, const Seg &m
         g.m0 = lane_read(mine.m0, src);
         g.m1 = lane_read(mine.m1, src);
         g.m2 = lane_read(mine.m2, src);
+        if constexpr (OPT) g.opt = lane_read(mine.opt, src);
+        else g.opt = 0u;
         if (k < cnt) {  // uniform over the group
-            if constexpr (CLS == 0) frame_small(a, g, lane);
-            else frame_stream<LPF>(a, g, lane);
+            if constexpr (CLS == 0) frame_small<OPT>(a, g, lane);
+            else frame_stream<OPT, LPF>(a, g, lane);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void tx_build_kernel(TbArgs a)
+template <bool OPT>
+__global__ __launch_bounds__(256) void tx_build_kernel(Args<OPT> a)
 {
     const int lane = (int)(threadIdx.x & 63u);
     const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), nwaves = gridDim.x * 4u;
@@ -335,11 +462,23 @@ __global__ __launch_bounds__(256) void tx_build_kernel(TbArgs a)
             flow = d1.x; g.seq = d1.y;
             g.ack = d2.x; g.lw = d2.y;
             g.idf = d3.x & 0x00FFFFFFu;
+            if constexpr (OPT) g.opt = d3.y;
         }
         const uint64_t so = ((uint64_t)g.s_hi << 32) | g.s_lo;
         const uint32_t L = g.lw & 0xFFFFu;
-        const bool valid = inb && flow < a.nflows && L <= RXG_TX_MAX_DATA && so <= a.payload_bytes &&
-                           (uint64_t)L <= a.payload_bytes - so;
+        uint32_t O = 0;
+        bool valid = inb && flow < a.nflows && L <= RXG_TX_MAX_DATA && so <= a.payload_bytes &&
+                     (uint64_t)L <= a.payload_bytes - so;
+        if constexpr (OPT) {
+            bool opt_ok = g.opt <= a.nopts;  // a block is read only once its index is known to be inside the table
+            if (opt_ok && g.opt != 0u) {
+                O = *reinterpret_cast<const uint32_t *>(a.opts + (g.opt - 1u)) & 0xFFu;  // rxg_tx_opt.len
+                opt_ok = O <= 40u && (O & 3u) == 0u;
+                if (!opt_ok) O = 0u;
+            }
+            g.idf |= O << 24;
+            valid = valid && opt_ok && L <= RXG_TX_MAX_DATA - O;
+        }
         if (valid) {
             const uint2 *f = reinterpret_cast<const uint2 *>(a.flows + flow);
             const uint2 f0 = f[0], f1 = f[1], f2 = f[2];
@@ -348,16 +487,16 @@ __global__ __launch_bounds__(256) void tx_build_kernel(TbArgs a)
             g.m1 = f2.x; g.m2 = f2.y;
             g.off = a.off64 ? a.off64[i] : a.slot0 + i * a.stride64;
         }
-        if (inb) a.len[i] = valid ? (uint16_t)(kHdr + L) : (uint16_t)0;
+        if (inb) a.len[i] = valid ? (uint16_t)(kHdr + O + L) : (uint16_t)0;
         built += (uint32_t)__popcll(__ballot(valid));
         skipped += (uint32_t)__popcll(__ballot(inb && !valid));
-        const int cls = valid ? class_of(L) : -1;
-        run_class<0>(a, cls, g, lane);
-        run_class<4>(a, cls, g, lane);
-        run_class<8>(a, cls, g, lane);
-        run_class<16>(a, cls, g, lane);
-        run_class<32>(a, cls, g, lane);
-        run_class<64>(a, cls, g, lane);
+        const int cls = valid ? class_of(kHdr + O + L) : -1;
+        run_class<OPT, 0>(a, cls, g, lane);
+        run_class<OPT, 4>(a, cls, g, lane);
+        run_class<OPT, 8>(a, cls, g, lane);
+        run_class<OPT, 16>(a, cls, g, lane);
+        run_class<OPT, 32>(a, cls, g, lane);
+        run_class<OPT, 64>(a, cls, g, lane);
     }
     // one atomic instruction per wave: lane 0 adds the built count, lane 1 the skipped
     if (a.stats && lane < 2 && (built | skipped) != 0u)
@@ -366,17 +505,18 @@ __global__ __launch_bounds__(256) void tx_build_kernel(TbArgs a)
 
 }  // namespace
 
-int tx_build_blocks_per_cu()
+int tx_build_blocks_per_cu(bool with_opts)
 {
     int n = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, tx_build_kernel, 256, 0);
+    const hipError_t e = with_opts ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, tx_build_kernel<true>, 256, 0)
+                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, tx_build_kernel<false>, 256, 0);
     return (e == hipSuccess && n > 0) ? n : 4;
 }
 
 hipError_t launch_tx_build(const LaunchTxBuild &B, hipStream_t st)
 {
     if (B.n == 0) return hipSuccess;
-    TbArgs a;
+    TbArgsOpt a;
     a.payload = B.payload;
     a.payload_bytes = B.payload_bytes;
     a.flows = B.flows;
@@ -392,7 +532,10 @@ hipError_t launch_tx_build(const LaunchTxBuild &B, hipStream_t st)
     a.nslices = (uint32_t)(((uint64_t)B.n + 63u) / 64u);
     uint32_t blocks = (a.nslices + 3u) / 4u;
     if (B.max_blocks && blocks > B.max_blocks) blocks = B.max_blocks;
-    hipLaunchKernelGGL(tx_build_kernel, dim3(blocks), dim3(256), 0, st, a);
+    a.opts = B.opts;
+    a.nopts = B.nopts;
+    if (B.with_opts) hipLaunchKernelGGL(tx_build_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(tx_build_kernel<false>, dim3(blocks), dim3(256), 0, st, static_cast<const TbArgs &>(a));
     return hipGetLastError();
 }
 

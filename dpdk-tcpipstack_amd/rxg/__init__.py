@@ -99,6 +99,8 @@ TX_SEG_DTYPE = np.dtype([("src_off", "<u8"), ("flow", "<u4"), ("seq", "<u4"), ("
 TX_SEND_DTYPE = np.dtype([("flow", "<u4"), ("next_seq", "<u4"), ("ack", "<u4"), ("src_off", "<u8"),
                           ("bytes", "<u4"), ("tcp_flags", "u1"), ("pad", "u1", (3,)), ("win_raw", "<u2"),
                           ("ip_id0", "<u2")], align=True)
+# one TCP option block of rxg_tx_build_opt_dev's table (rxg_tx_opt)
+TX_OPT_DTYPE = np.dtype([("len", "u1"), ("reserved0", "u1", (5,)), ("bytes", "u1", (40,)), ("reserved1", "u1", (2,))])
 
 
 def rec8_pack(r16: np.ndarray) -> np.ndarray:
@@ -221,6 +223,17 @@ class DevTxBuild(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class TxOpt(C.Structure):
+    """rxg_tx_opt (TX_OPT_DTYPE): one TCP option block."""
+    _fields_ = [("len", C.c_uint8), ("reserved0", C.c_uint8 * 5), ("bytes", C.c_uint8 * 40),
+                ("reserved1", C.c_uint8 * 2)]
+
+
+class DevTxBuildOpt(C.Structure):
+    """rxg_dev_tx_build_opt."""
+    _fields_ = [("b", DevTxBuild), ("opts", C.c_void_p), ("nopts", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class DevTxReset(C.Structure):
     """rxg_dev_tx_reset."""
     _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
@@ -339,6 +352,11 @@ def load_library(path: str = LIB_PATH):
         "rxg_tx_cksum_dev": (C.c_int, [vp, C.POINTER(DevTxBatch), vp]),
         "rxg_tx_build_dev": (C.c_int, [vp, C.POINTER(DevTxBuild), vp]),
         "rxg_tx_plan": (C.c_int64, [vp, u32, u32, vp, u64, vp]),
+        "rxg_tx_build_opt_dev": (C.c_int, [vp, C.POINTER(DevTxBuildOpt), vp]),
+        "rxg_tx_opt_set": (C.c_int, [vp, vp, u32]),
+        "rxg_tx_opt_timestamp": (C.c_int, [vp, u32, u32]),
+        "rxg_tx_opt_ref_ack": (C.c_int, [vp]),
+        "rxg_tx_plan_opt": (C.c_int64, [vp, u32, u32, vp, vp, u32, vp, u64, vp]),
         "rxg_tx_reset_dev": (C.c_int, [vp, C.POINTER(DevTxReset), vp]),
         "rxg_reset_set_id": (None, [vp, C.c_uint16]),
         "rxg_reset_attach": (C.c_int, [vp, vp, vp, u64]),
@@ -497,6 +515,66 @@ def tx_plan(sends, mss: int):
     if rc != cap:
         raise RxgError(f"rxg_tx_plan failed ({rc})")
     return segs, nxt
+
+
+def _tx_opt_block(rc: int, o: np.ndarray, what: str) -> np.ndarray:
+    if rc < 0:
+        raise RxgError(f"{what} failed ({rc})")
+    return o[0]
+
+
+def tx_opt_set(data: bytes) -> np.ndarray:
+    """rxg_tx_opt_set: a TX_OPT_DTYPE block holding `data` (at most 40 bytes), zero-padded to a
+    multiple of 4."""
+    o = np.zeros(1, dtype=TX_OPT_DTYPE)
+    raw = np.frombuffer(bytes(data), np.uint8)
+    return _tx_opt_block(load_library().rxg_tx_opt_set(_ptr(o), _ptr(raw) if len(raw) else None, len(raw)), o,
+                         "rxg_tx_opt_set")
+
+
+def tx_opt_timestamp(tsval: int, tsecr: int) -> np.ndarray:
+    """rxg_tx_opt_timestamp: the 12-byte block NOP NOP timestamp a data segment carries."""
+    o = np.zeros(1, dtype=TX_OPT_DTYPE)
+    return _tx_opt_block(load_library().rxg_tx_opt_timestamp(_ptr(o), tsval & 0xFFFFFFFF, tsecr & 0xFFFFFFFF), o,
+                         "rxg_tx_opt_timestamp")
+
+
+def tx_opt_ref_ack() -> np.ndarray:
+    """rxg_tx_opt_ref_ack: the 20-byte block of the reference's ACK (sendtcpack, tcp_out.c:255-262)."""
+    o = np.zeros(1, dtype=TX_OPT_DTYPE)
+    return _tx_opt_block(load_library().rxg_tx_opt_ref_ack(_ptr(o)), o, "rxg_tx_opt_ref_ack")
+
+
+def tx_plan_opt(sends, mss: int, send_opt, opts):
+    """rxg_tx_plan_opt: tx_plan where send j's segments carry block send_opt[j] (0: none, k:
+    opts[k - 1]) in `reserved` and at most mss - len payload bytes.  send_opt None: tx_plan's
+    output.  Returns (segs TX_SEG_DTYPE, next_seq u32 per send)."""
+    if send_opt is None:
+        return tx_plan(sends, mss)
+    lib = load_library()
+    if not isinstance(sends, np.ndarray):
+        rows = list(sends)
+        sends = np.zeros(len(rows), dtype=TX_SEND_DTYPE)
+        for i, r in enumerate(rows):
+            for k, v in zip(("flow", "next_seq", "ack", "src_off", "bytes", "tcp_flags", "win_raw", "ip_id0"), r):
+                sends[i][k] = v
+    sends = np.ascontiguousarray(sends, dtype=TX_SEND_DTYPE)
+    send_opt = np.ascontiguousarray(send_opt, dtype=np.uint32)
+    opts = np.ascontiguousarray(opts, dtype=TX_OPT_DTYPE).reshape(-1)
+    if len(send_opt) != len(sends):
+        raise ValueError("tx_plan_opt: one send_opt entry per send")
+    if not 0 < mss <= TX_MAX_DATA:
+        raise RxgError(f"rxg_tx_plan_opt failed (-22): mss {mss}")
+    # room for the segments of a call that succeeds (one that fails writes nothing)
+    olen = [int(opts[k - 1]["len"]) if 0 < k <= len(opts) else 0 for k in send_opt.tolist()]
+    cap = int(sum(max(1, -(-int(b) // max(1, mss - o))) for b, o in zip(sends["bytes"], olen)))
+    segs = np.zeros(cap, dtype=TX_SEG_DTYPE)
+    nxt = np.zeros(len(sends), dtype=np.uint32)
+    rc = lib.rxg_tx_plan_opt(_ptr(sends), len(sends), mss, _ptr(send_opt), _ptr(opts) if len(opts) else None,
+                             len(opts), _ptr(segs), cap, _ptr(nxt))
+    if rc < 0:
+        raise RxgError(f"rxg_tx_plan_opt failed ({rc})")
+    return segs[:rc].copy(), nxt
 
 
 def reset_set_id(frame64, ip_id: int) -> bytes:
@@ -787,6 +865,15 @@ class Engine:
         b = DevTxBuild(payload, payload_bytes, flows, nflows, n, segs, frames, off64, slot0, stride64, lens, stats)
         _check(_lib.rxg_tx_build_dev(self.ctx, C.byref(b), stream), "rxg_tx_build_dev")
 
+    def tx_build_opt_dev(self, payload: int, payload_bytes: int, flows: int, nflows: int, segs: int, n: int,
+                         frames: int, lens: int, opts: int | None, nopts: int, off64: int | None = None,
+                         slot0: int = 0, stride64: int = 0, stats: int | None = None, stream=None):
+        """rxg_tx_build_opt_dev: tx_build_dev where segment i carries the option block its
+        `reserved` names (0: none, k: the k-th rxg_tx_opt at `opts`)."""
+        b = DevTxBuildOpt(DevTxBuild(payload, payload_bytes, flows, nflows, n, segs, frames, off64, slot0, stride64,
+                                     lens, stats), opts, nopts, 0)
+        _check(_lib.rxg_tx_build_opt_dev(self.ctx, C.byref(b), stream), "rxg_tx_build_opt_dev")
+
     def tx_reset_dev(self, frames: int, lens: int, n: int, recs: int, rec_kind: int, out: int, idx: int, cap: int,
                      count: int, off64: int | None = None, slot0: int = 0, stride64: int = 0, ip_id0: int = 0,
                      src_mac: bytes = REF_SRC_MAC, stream=None):
@@ -811,18 +898,22 @@ class Engine:
         return p.value if rc == 1 else None
 
     def tx_build(self, payload: np.ndarray, flows: np.ndarray, segs: np.ndarray, off64=None, slot0: int = 0,
-                 stride64: int = 0):
+                 stride64: int = 0, opts=None):
         """Upload the inputs, build the segments, sync.  Returns (arena u8, lens u16, stats u64[2]
         = built, skipped); the arena covers the slots the call may write (frames of up to
-        ceil((54 + max data_len) / 64) slots), like tx_arena's."""
+        ceil((54 + max data_len) / 64) slots), like tx_arena's.  opts (TX_OPT_DTYPE): the build
+        goes through rxg_tx_build_opt_dev, segs["reserved"] naming each segment's block (the
+        arena then allows for 40 option bytes)."""
         segs = np.ascontiguousarray(segs, dtype=TX_SEG_DTYPE)
         flows = np.ascontiguousarray(flows, dtype=TX_FLOW_DTYPE)
         payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        if opts is not None:
+            opts = np.ascontiguousarray(opts, dtype=TX_OPT_DTYPE).reshape(-1)
         n = len(segs)
         if n == 0:
             return np.zeros(0, np.uint8), np.zeros(0, np.uint16), np.zeros(2, np.uint64)
         ok = segs["data_len"] <= TX_MAX_DATA
-        span = (54 + int(segs["data_len"][ok].max() if ok.any() else 0) + 63) // 64
+        span = (54 + (40 if opts is not None else 0) + int(segs["data_len"][ok].max() if ok.any() else 0) + 63) // 64
         if off64 is not None:
             off64 = np.ascontiguousarray(off64, dtype=np.uint32)
             slots = int(off64.max()) + span
@@ -832,16 +923,22 @@ class Engine:
         padded[:payload.size] = payload
         dp, df, ds = self.to_device(padded), self.to_device(flows), self.to_device(segs)
         do = self.to_device(off64) if off64 is not None else None
+        dopt = self.to_device(opts) if opts is not None and len(opts) else None
         da, dl, dst = self.alloc(slots * 64), self.alloc(n * 2), self.alloc(16)
         try:
             _check(_lib.rxg_memset_dev(self.ctx, da.ptr, 0, slots * 64, None), "rxg_memset_dev")
             _check(_lib.rxg_memset_dev(self.ctx, dst.ptr, 0, 16, None), "rxg_memset_dev")
-            self.tx_build_dev(dp.ptr, payload.size, df.ptr, len(flows), ds.ptr, n, da.ptr, dl.ptr,
-                              do.ptr if do else None, slot0, stride64, dst.ptr)
+            if opts is None:
+                self.tx_build_dev(dp.ptr, payload.size, df.ptr, len(flows), ds.ptr, n, da.ptr, dl.ptr,
+                                  do.ptr if do else None, slot0, stride64, dst.ptr)
+            else:
+                self.tx_build_opt_dev(dp.ptr, payload.size, df.ptr, len(flows), ds.ptr, n, da.ptr, dl.ptr,
+                                      dopt.ptr if dopt else None, len(opts), do.ptr if do else None, slot0, stride64,
+                                      dst.ptr)
             self.sync()
             return da.download(np.uint8, slots * 64), dl.download(np.uint16, n), dst.download(np.uint64, 2)
         finally:
-            for d in (dp, df, ds, do, da, dl, dst):
+            for d in (dp, df, ds, do, dopt, da, dl, dst):
                 if d is not None:
                     d.free()
 

@@ -529,7 +529,8 @@ typedef struct rxg_tx_seg { /* 32 bytes */
     uint16_t ip_id;         /* stored without a byte swap, as ip.c:106 does               */
     uint8_t tcp_flags;
     uint8_t pad;
-    uint32_t reserved;
+    uint32_t reserved;      /* ignored by rxg_tx_build_dev; rxg_tx_build_opt_dev: the segment's
+                               option block, 0 = none, k = opts[k - 1]                       */
 } rxg_tx_seg;
 
 typedef struct rxg_dev_tx_build {
@@ -567,6 +568,91 @@ typedef struct rxg_tx_send {
 } rxg_tx_send;
 int64_t rxg_tx_plan(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss, rxg_tx_seg *out, uint64_t cap,
                     uint32_t *next_seq_out);
+
+/* ------------------------------------------------------------------------- */
+/* Transmit segment build with TCP options: rxg_tx_build_dev for segments      */
+/* that carry an option block between the TCP header and the payload, as the   */
+/* reference's own ACK does (sendack -> sendtcpack, tcp_out.c:251-289: a       */
+/* 40-byte TCP header) and as every data segment to a peer that negotiated     */
+/* timestamps must.  The host fills a table of option blocks; a segment names  */
+/* its block, the device needs no per-connection state for it.                 */
+/*                                                                             */
+/* In this call only, rxg_tx_seg.reserved selects the block: 0 = no options,   */
+/* k in 1..nopts = opts[k - 1], O = opts[k - 1].len (0 otherwise).  Frame i    */
+/* holds 54 header bytes, O option bytes (bytes[0..O) as they stand, at frame  */
+/* bytes 54 .. 54 + O), data_len payload bytes and zeros up to the next        */
+/* 64-byte boundary; nothing past that boundary is written.  len[i] = 54 + O + */
+/* data_len.  Header fields are rxg_tx_build_dev's except                      */
+/*   IPv4      total_length htons(40 + O + data_len)                           */
+/*   TCP       data_off (5 + O / 4) << 4; cksum over pseudo || header ||       */
+/*             options || payload, the pseudo-header's length htons(20 + O +   */
+/*             data_len).                                                      */
+/* The payload is read as by rxg_tx_build_dev (16-byte chunks overlapping      */
+/* [src_off, src_off + data_len) only; data_len 0: none); of a block, its      */
+/* 48 bytes.                                                                   */
+/*                                                                             */
+/* A segment is skipped under rxg_tx_build_dev's rules and when reserved >     */
+/* nopts, when its block's len is over 40 or not a multiple of 4, or when      */
+/* data_len > RXG_TX_MAX_DATA - O: len[i] = 0, nothing written to its frame,   */
+/* stats[1] counts it; its flow index, source offset and block index are never */
+/* followed, and a block is read only once reserved <= nopts is established.   */
+/* -EINVAL: rxg_tx_build_dev's cases, opts not 16-byte aligned, opts NULL with */
+/* nopts != 0.  n == 0 does nothing.  With every reserved == 0 the frames, len */
+/* and stats are rxg_tx_build_dev's byte for byte.                             */
+/* ------------------------------------------------------------------------- */
+
+/* One TCP option block, 48 bytes, tables 16-byte aligned.  bytes[0..len) are stored at frame
+   bytes 54 .. 54+len as they stand; len is 0, 4, .. 40.  The layout puts bytes[] at offset 6,
+   so the three 16-byte chunks of the struct are the images of frame chunks 3, 4 and 5
+   (frame bytes 48-95) from byte 54 on: the kernel loads them aligned, no shift.  Bytes of
+   bytes[] at or past len, and the reserved fields, are ignored (not required to be zero). */
+typedef struct rxg_tx_opt {
+    uint8_t len;
+    uint8_t reserved0[5];
+    uint8_t bytes[40];
+    uint8_t reserved1[2];
+} rxg_tx_opt;
+
+typedef struct rxg_dev_tx_build_opt {
+    rxg_dev_tx_build b;     /* everything rxg_tx_build_dev takes, same rules           */
+    const rxg_tx_opt *opts; /* dev, 16-byte aligned; may be NULL when nopts == 0       */
+    uint32_t nopts;
+    uint32_t pad;
+} rxg_dev_tx_build_opt;
+int rxg_tx_build_opt_dev(rxg_ctx *ctx, const rxg_dev_tx_build_opt *b, void *stream);
+
+/* Host helpers for option blocks (no context, no GPU).
+   rxg_tx_opt_set: n <= 40 bytes copied and padded with zero bytes to a multiple of 4 (zero is
+   kind 0, end of option list: what the reference's memset(nop, 0, pad) writes, tcp_out.c:262),
+   the rest of the struct zeroed.  Returns the padded length; -EINVAL for n > 40 or a NULL
+   argument (bytes may be NULL when n == 0).
+   rxg_tx_opt_timestamp: the 12 bytes 01 01 08 0A htonl(tsval) htonl(tsecr) (RFC 7323
+   appendix A), the block a data segment carries.  Returns 12.
+   rxg_tx_opt_ref_ack: the 20 bytes sendtcpack builds (tcp_out.c:255-262, structs tcp.h:37-54,
+   all packed).  Each add_*_option prepends, so the last one called comes first in the frame:
+     08 0A 18 19 03 00 00 00 00 00   timestamp, value 203032 and echo 0 stored without a byte
+                                     swap (add_timestamp_option, tcp_out.c:66-74)
+     02 04 05 14                     MSS htons(1300)
+     03 03 07                        window scale 7
+     00 00 00                        pad
+   This is the order gcc's left-to-right evaluation of the operands of `+` in tcp_out.c:255
+   gives; C leaves that order unspecified, and it has not been confirmed on a build of the
+   reference.  The reference appends its pad after the data (rte_pktmbuf_append,
+   tcp_out.c:261), rxg pads inside the block: for sendack, which sends no data, the two are
+   the same bytes.  With this block, tcp_flags ACK, win_raw 12000 and data_len 0 the built
+   frame is sendack's.  Returns 20. */
+int rxg_tx_opt_set(rxg_tx_opt *o, const uint8_t *bytes, uint32_t n);
+int rxg_tx_opt_timestamp(rxg_tx_opt *o, uint32_t tsval, uint32_t tsecr);
+int rxg_tx_opt_ref_ack(rxg_tx_opt *o);
+
+/* rxg_tx_plan for sends that carry options: every segment of send j gets reserved =
+   send_opt[j] and at most mss - O payload bytes, O that block's len (the options come out of
+   the MSS, RFC 6691).  send_opt NULL: rxg_tx_plan's output exactly.  -EINVAL additionally for
+   send_opt[j] > nopts, a block length that is not 0..40 in steps of 4, mss <= O, or opts NULL
+   where a block is named; nothing is written in these cases. */
+int64_t rxg_tx_plan_opt(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss, const uint32_t *send_opt,
+                        const rxg_tx_opt *opts, uint32_t nopts, rxg_tx_seg *out, uint64_t cap,
+                        uint32_t *next_seq_out);
 
 /* ------------------------------------------------------------------------- */
 /* Reset replies built on the device from a burst's records: what send_reset   */

@@ -7,10 +7,18 @@ rounds on one stream,
      bytes into pre-headered frames, then rxg_tx_cksum_dev over them; the copy is torch's
      copy_ of a strided uint8 view (b) or the runtime's hipMemcpy2DAsync (b2)
   c  rxg_tx_cksum_dev alone over the same frames
+and, where the library has rxg_tx_build_opt_dev,
+  a0 rxg_tx_build_opt_dev over the same descriptors (every reserved == 0: the option kernel
+     doing the plain build's work)
+  o  rxg_tx_build_opt_dev over 2^20 segments of --opt-len (1448) payload bytes that each carry
+     the 12-byte timestamp block (one block in the table)
+  bo (b) for those frames: the strided copy to frame byte 66 of frames that hold their headers
+     and options already, then rxg_tx_cksum_dev
 each over `--sets` rotating sets of buffers (a set is 3.1 GB at the default size, twelve times
 the Infinity Cache, and a launch never meets the lines the launch before it left there).
 Fractions of 8 TB/s are on the build's algorithmic bytes per segment: data_len + 32 + 64 *
-ceil((54 + data_len) / 64) + 2.
+ceil((54 + data_len) / 64) + 2; for (o) and (bo): data_len + 32 + 64 * ceil((66 + data_len) / 64)
++ 2, and 48 for the one block.  --variants a,o,.. times a subset (an older library: a, b, b2, c).
   python scripts/txbuildbench.py [--n 1048576 --len 1460 --rounds 5 --iters 20]"""
 import argparse
 import ctypes as C
@@ -35,8 +43,12 @@ def main():
     ap.add_argument("--sets", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--opt-len", type=int, default=1448)
+    ap.add_argument("--variants", default="")
     args = ap.parse_args()
     n, L, stride = args.n, args.len, args.stride64
+    LO, O = args.opt_len, 12  # the option legs: LO payload bytes after the 12-byte timestamp block
+    assert 54 + O + LO <= stride * 64 and LO <= L
     assert torch.cuda.is_available(), "txbuildbench needs a GPU"
     assert 54 + L <= stride * 64
     dev = torch.device("cuda:0")
@@ -66,6 +78,13 @@ def main():
     def dev_of(a):
         return torch.from_numpy(a.view(np.uint8).copy()).to(dev)
     d_flows, d_segs = dev_of(flows), dev_of(segs)
+    has_opt = hasattr(rxg.load_library(), "rxg_tx_build_opt_dev")
+    if has_opt:
+        segs_o = segs.copy()
+        segs_o["src_off"] = np.arange(n, dtype=np.uint64) * LO
+        segs_o["data_len"], segs_o["reserved"] = LO, 1
+        d_segs_o = dev_of(segs_o)
+        d_opts = dev_of(np.array([rxg.tx_opt_timestamp(0x01020304, 0x05060708)], dtype=rxg.TX_OPT_DTYPE))
     d_stats = torch.zeros(2, dtype=torch.int64, device=dev)
     d_off = torch.arange(n, dtype=torch.int32, device=dev) * stride  # (c)'s offsets as a list
     pbytes = (n * L + 15) // 16 * 16
@@ -75,10 +94,24 @@ def main():
         sets.append(dict(pay=pay, built=torch.zeros(n * stride * 64, dtype=torch.uint8, device=dev),
                          pre=torch.zeros(n * stride * 64, dtype=torch.uint8, device=dev),
                          len=torch.zeros(n, dtype=torch.int16, device=dev)))
+        if has_opt:
+            sets[-1].update(pre_o=torch.zeros(n * stride * 64, dtype=torch.uint8, device=dev),
+                            len_o=torch.zeros(n, dtype=torch.int16, device=dev))
 
     def build(s, frames):
         eng.tx_build_dev(s["pay"].data_ptr(), n * L, d_flows.data_ptr(), args.flows, d_segs.data_ptr(), n,
                          frames.data_ptr(), s["len"].data_ptr(), None, 0, stride, d_stats.data_ptr(), stream=st)
+
+    def build_opt(s, frames, d_sg, lens, nbytes):
+        eng.tx_build_opt_dev(s["pay"].data_ptr(), nbytes, d_flows.data_ptr(), args.flows, d_sg.data_ptr(), n,
+                             frames.data_ptr(), lens.data_ptr(), d_opts.data_ptr(), 1, None, 0, stride,
+                             d_stats.data_ptr(), stream=st)
+
+    def copy_in_o(s):  # (bo): the payload bytes behind headers and options that are there already
+        s["pre_o"].view(n, stride * 64)[:, 54 + O:54 + O + LO].copy_(s["pay"][:n * LO].view(n, LO))
+
+    def cksum_o(s):
+        eng.tx_cksum_dev(s["pre_o"].data_ptr(), d_off.data_ptr(), s["len_o"].data_ptr(), n, stream=st)
 
     def copy_in(s):  # the payload bytes into place, device to device
         s["pre"].view(n, stride * 64)[:, 54:54 + L].copy_(s["pay"][:n * L].view(n, L))
@@ -111,6 +144,27 @@ def main():
     torch.cuda.synchronize()
     for s in sets:
         assert torch.equal(s["built"], s["pre"]), "copy + rxg_tx_cksum_dev and rxg_tx_build_dev differ"
+    if has_opt:
+        variants["a0_tx_build_opt_reserved0"] = lambda s: build_opt(s, s["built"], d_segs, s["len"], n * L)
+        variants["o_tx_build_opt_ts12"] = lambda s: build_opt(s, s["built"], d_segs_o, s["len_o"], n * LO)
+        variants["bo_copy_then_cksum_ts12"] = lambda s: (copy_in_o(s), cksum_o(s))
+        # and so do the option legs: (a0) the plain build's frames, (o) and (bo) the same frames
+        for s in sets:
+            s["built"].zero_()
+            variants["a0_tx_build_opt_reserved0"](s)
+            torch.cuda.synchronize()
+            assert torch.equal(s["built"], s["pre"]), "rxg_tx_build_opt_dev with reserved 0 and rxg_tx_build_dev differ"
+            build_opt(s, s["pre_o"], d_segs_o, s["len_o"], n * LO)  # (bo)'s pre-headered frames
+            s["built"].zero_()
+            variants["o_tx_build_opt_ts12"](s)
+            variants["bo_copy_then_cksum_ts12"](s)
+            torch.cuda.synchronize()
+            assert torch.equal(s["built"], s["pre_o"]), "copy + rxg_tx_cksum_dev and rxg_tx_build_opt_dev differ"
+            assert int(s["len_o"][0]) == 54 + O + LO and int(s["built"].view(n, stride * 64)[n - 1, 46]) == 0x80
+    only = [v for v in args.variants.split(",") if v]
+    if only:
+        variants = {k: f for k, f in variants.items() if k.split("_")[0] in only}
+        assert variants, "no such variant"
 
     res = {k: [] for k in variants}
     for _ in range(args.rounds):
@@ -123,10 +177,13 @@ def main():
                 e.record()
             torch.cuda.synchronize()
             res[name].append(float(np.median([a.elapsed_time(e) for a, e in evs])))
-    alg = n * (L + 32 + 64 * ((54 + L + 63) // 64) + 2)
+    alg_plain = n * (L + 32 + 64 * ((54 + L + 63) // 64) + 2)
+    alg_opt = n * (LO + 32 + 64 * ((54 + O + LO + 63) // 64) + 2) + 48
     for name, ms in res.items():
         med = float(np.median(ms))
-        print(json.dumps({"variant": name, "n": n, "data_len": L, "us": round(med * 1e3, 1),
+        alg = alg_opt if name.endswith("_ts12") else alg_plain
+        print(json.dumps({"variant": name, "n": n, "data_len": LO if name.endswith("_ts12") else L,
+                          "us": round(med * 1e3, 1),
                           "rounds_us": [round(x * 1e3, 1) for x in ms],
                           "spread_pct": round(100 * (max(ms) - min(ms)) / med, 2),
                           "alg_bytes": alg, "frac_8TBs": round(alg / (med * 1e-3) / 8e12, 4)}), flush=True)
