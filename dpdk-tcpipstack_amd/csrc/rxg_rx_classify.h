@@ -224,7 +224,10 @@ __device__ __forceinline__ uint32_t tuple_lookup(const RxArgs &a, const Probe &P
 #pragma unroll
     for (int k = 0; k < kSlotsPerBucket; ++k) {
         const bool m = P.s[k].x == ports && P.s[k].y == dst_raw && P.s[k].z == src_host;
-        v = m ? P.s[k].w : v;  // a free slot holds kEmpty: a match there is no hit
+        // A free slot holds kEmpty (all ones) and key words 0: the all-zero tuple matches it too,
+        // before or after its own slot.  A key sits in one slot only, so the AND keeps that
+        // slot's value whatever the order, and a match on free slots alone stays kEmpty.
+        v = m ? (v & P.s[k].w) : v;
         empty |= P.s[k].w == kEmpty;
     }
     const bool more = v == kEmpty && !empty;
