@@ -87,6 +87,7 @@ struct rxg_ctx {
     uint32_t grid_txb = 0;          // rxg_tx_build_dev's occupancy grid (set at init)
     uint32_t grid_txbo = 0;         // rxg_tx_build_opt_dev's
     uint32_t grid_txr = 0;          // rxg_tx_reset_dev's (its build pass)
+    uint32_t grid_rxo = 0;          // rxg_rx_opts_dev's
     // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
     uint32_t grid[2][4] = {};
     rxg::PackPool pack_pool;  // rxg_rx_burst's packing threads
@@ -171,6 +172,11 @@ struct rxg_ctx {
     uint8_t *rst_host = nullptr;
     const uint32_t *rst_idx = nullptr;
     uint64_t rst_n = 0, rst_cur = 0;
+    // rxg_rx_opts_attach: a host copy of a rxg_rx_opts_dev call's records for the replay that
+    // follows (cleared when it returns); rxg_rx_opt_current answers from it
+    const rxg_rx_opt *opt_host = nullptr;
+    uint32_t opt_n = 0;
+    bool opt_live = false;  // the running replay's burst has opt_n frames
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;

@@ -86,6 +86,7 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         c->grid_txb = cus * (uint32_t)tx_build_blocks_per_cu(false);  // rxg_tx_build_dev's occupancy grid
         c->grid_txbo = cus * (uint32_t)tx_build_blocks_per_cu(true);  // rxg_tx_build_opt_dev's
         c->grid_txr = cus * (uint32_t)tx_reset_blocks_per_cu();  // rxg_tx_reset_dev's
+        c->grid_rxo = cus * (uint32_t)rx_opts_blocks_per_cu();  // rxg_rx_opts_dev's
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -815,6 +816,41 @@ extern "C" int rxg_tx_reset_dev(rxg_ctx *c, const rxg_dev_tx_reset *b, void *str
     // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
     if (b->n) HIP_OK(hipEventRecord(c->rst_ev, st));
     HIP_OK(e);
+    return 0;
+}
+
+static_assert(sizeof(rxg_rx_opt) == 16 && sizeof(rxg_dev_rx_opts) == 56, "received-option layouts");
+
+extern "C" int rxg_rx_opts_dev(rxg_ctx *c, const rxg_dev_rx_opts *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_rx_opts_dev: NULL argument");
+    if (!b->frames || !b->len || !b->recs || !b->out) return fail(-EINVAL, "rxg_rx_opts_dev: NULL device pointer");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_rx_opts_dev: rec_kind %u", b->rec_kind);
+    const uintptr_t rec_align = b->rec_kind == RXG_REC8 ? 8u : 16u;  // (as rxg_rx_burst_dev)
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 15u) || ((uintptr_t)b->off64 & 3u) ||
+        ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align - 1u)))
+        return fail(-EINVAL, "rxg_rx_opts_dev: frames and out need 16-byte, off64 4-byte, len 2-byte, recs %u-byte "
+                             "alignment", (unsigned)rec_align);
+    if (!b->off64) {
+        if (!b->stride64) return fail(-EINVAL, "rxg_rx_opts_dev: stride64 0");
+        if (b->n && (uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
+            return fail(-EINVAL, "rxg_rx_opts_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
+    }
+    if (!b->n) return 0;
+    int rc = set_device(c);
+    if (rc) return rc;
+    LaunchRxOpts L;
+    L.frames = (const uint8_t *)b->frames;
+    L.off64 = b->off64;
+    L.len = b->len;
+    L.slot0 = b->slot0;
+    L.stride64 = b->stride64;
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.out = (uint8_t *)b->out;
+    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_rxo ? c->grid_rxo : 1024u);  // (as grid_for)
+    HIP_OK(launch_rx_opts(L, pick(c, stream)));
     return 0;
 }
 

@@ -200,6 +200,21 @@ struct LaunchTxReset {
 hipError_t launch_tx_reset(const LaunchTxReset &R, hipStream_t st);
 size_t tx_reset_count_bytes(uint32_t n);  // the slice-count buffer a call of n frames needs
 int tx_reset_blocks_per_cu();  // resident 256-thread workgroups per CU of the build pass
+// rxg_rxopt.hip: the TCP options of a burst's segments (rxg_rx_opts_dev), one launch on `st`
+// (n == 0: none)
+struct LaunchRxOpts {
+    const uint8_t *frames;
+    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
+    const uint16_t *len;
+    uint32_t slot0, stride64;
+    uint32_t n;
+    uint32_t rec_kind;
+    const uint8_t *recs;
+    uint8_t *out;           // n rxg_rx_opt records
+    uint32_t max_blocks;    // grid cap (grid-stride over 64-frame slices); 0 = none
+};
+hipError_t launch_rx_opts(const LaunchRxOpts &R, hipStream_t st);
+int rx_opts_blocks_per_cu();  // resident 256-thread workgroups per CU of its kernel
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

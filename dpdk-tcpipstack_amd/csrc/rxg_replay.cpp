@@ -1,7 +1,8 @@
 // rxg_replay.cpp — the per-packet replay of a classified burst into the caller's handlers
 // (rxg_rx_replay: the reference's ether_in -> ip_in -> tcp_in order, re-classifying what a
 // handler's table write changed), the payload hand-off (rxg_payload_gather_dev, rxg_rcv_set,
-// rxg_payload_take), the prebuilt resets' hand-out (rxg_reset_attach, rxg_reset_take) and the
+// rxg_payload_take), the prebuilt resets' hand-out (rxg_reset_attach, rxg_reset_take), the
+// parsed options' (rxg_rx_opts_attach, rxg_rx_opt_current) and the
 // one-frame rxg_ether_in.
 #include <hip/hip_runtime.h>
 
@@ -171,6 +172,26 @@ extern "C" int rxg_reset_take(rxg_ctx *c, uint16_t ip_id, void **frame_out)
     return 1;
 }
 
+// ------------------------------------------------------------------ parsed options ---
+extern "C" int rxg_rx_opts_attach(rxg_ctx *c, const rxg_rx_opt *opts_host, uint32_t n)
+{
+    if (!c || (n && !opts_host)) return fail(-EINVAL, "rxg_rx_opts_attach: NULL argument");
+    c->opt_host = n ? opts_host : nullptr;
+    c->opt_n = n;
+    return 0;
+}
+
+// Record replay_pos of the attached copy: options do not depend on the mirror, so the record
+// of a packet the replay re-classified is as good as any other's.
+extern "C" int rxg_rx_opt_current(rxg_ctx *c, const rxg_rx_opt **out)
+{
+    if (!c || !out) return fail(-EINVAL, "rxg_rx_opt_current: NULL argument");
+    const int64_t pos = c->replay_pos;
+    if (pos < 0 || !c->opt_host || !c->opt_live || pos >= (int64_t)c->opt_n) return 0;
+    *out = c->opt_host + pos;
+    return 1;
+}
+
 // ------------------------------------------------------------------------- replay ---
 static inline bool rec_is_tcp(const rxg_rec16 &r)
 {
@@ -283,6 +304,9 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
             c->rst_host = nullptr;
             c->rst_idx = nullptr;
             c->rst_n = c->rst_cur = 0;
+            c->opt_host = nullptr;
+            c->opt_n = 0;
+            c->opt_live = false;
         }
     } pos_guard{c};
     if (!ops || (n && (!mbufs || !frames || !recs)))
@@ -295,6 +319,7 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
     // the re-classify launches and the counter correction run on this context's device
     // (a group replays several contexts from one thread, rxg_group.cpp)
     if (int rc = set_device(c)) return rc;
+    c->opt_live = c->opt_host && c->opt_n == n;  // (rxg_rx_opts_attach) the copy is this burst's
     std::vector<rxg_rec16> &cur = c->rp_cur;
     cur.resize(n);
     if (stride == RXG_REC8)

@@ -9,6 +9,7 @@ The reference surface this mirrors (rajneshrat/dpdk-tcpipstack, tcp_ip_stack/):
   tcbs[] writes (alloc_tcb, remove_tcb, state) -> Engine.tcb_upsert / tcb_remove / tcb_set_state
   ip_out's two checksums (ip.c:97-118)        -> Engine.tx_cksum_dev
   send_reset per offender (tcp_out.c:103-146) -> Engine.tx_reset_dev, reset_attach / reset_take
+  (no counterpart: received TCP options)     -> Engine.rx_opts_dev, rx_opt_parse, rx_opts_attach / rx_opt_current
 """
 from __future__ import annotations
 
@@ -101,6 +102,12 @@ TX_SEND_DTYPE = np.dtype([("flow", "<u4"), ("next_seq", "<u4"), ("ack", "<u4"), 
                           ("ip_id0", "<u2")], align=True)
 # one TCP option block of rxg_tx_build_opt_dev's table (rxg_tx_opt)
 TX_OPT_DTYPE = np.dtype([("len", "u1"), ("reserved0", "u1", (5,)), ("bytes", "u1", (40,)), ("reserved1", "u1", (2,))])
+# received TCP options (rxg_rx_opts_dev, rxg_rx_opt_parse): rxg_rx_opt and its RXG_O_* flags
+RX_OPT_DTYPE = np.dtype([("tsval", "<u4"), ("tsecr", "<u4"), ("mss", "<u2"), ("wscale", "u1"), ("nsack", "u1"),
+                         ("sack_off", "u1"), ("opt_len", "u1"), ("flags", "<u2")])
+assert RX_OPT_DTYPE.itemsize == 16
+(O_PARSED, O_MSS, O_WSCALE, O_SACK_PERM, O_SACK, O_TS, O_OTHER, O_MALFORMED, O_CUT,
+ O_BAD_DOFF) = (1 << k for k in range(10))
 
 
 def rec8_pack(r16: np.ndarray) -> np.ndarray:
@@ -245,6 +252,19 @@ class DevTxReset(C.Structure):
 TX_RESET = DevTxReset
 
 
+class RxOpt(C.Structure):
+    """rxg_rx_opt (RX_OPT_DTYPE): the parsed options of one frame."""
+    _fields_ = [("tsval", C.c_uint32), ("tsecr", C.c_uint32), ("mss", C.c_uint16), ("wscale", C.c_uint8),
+                ("nsack", C.c_uint8), ("sack_off", C.c_uint8), ("opt_len", C.c_uint8), ("flags", C.c_uint16)]
+
+
+class DevRxOpts(C.Structure):
+    """rxg_dev_rx_opts."""
+    _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
+                ("stride64", C.c_uint32), ("n", C.c_uint32), ("rec_kind", C.c_uint32), ("recs", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
 class PktView(C.Structure):
     _fields_ = [("buf_addr", C.c_void_p), ("data_off", C.c_uint16), ("data_len", C.c_uint16),
                 ("pad", C.c_uint32)]
@@ -361,6 +381,10 @@ def load_library(path: str = LIB_PATH):
         "rxg_reset_set_id": (None, [vp, C.c_uint16]),
         "rxg_reset_attach": (C.c_int, [vp, vp, vp, u64]),
         "rxg_reset_take": (C.c_int, [vp, C.c_uint16, C.POINTER(vp)]),
+        "rxg_rx_opts_dev": (C.c_int, [vp, C.POINTER(DevRxOpts), vp]),
+        "rxg_rx_opt_parse": (C.c_int, [C.c_char_p, u32, C.POINTER(RxOpt)]),
+        "rxg_rx_opts_attach": (C.c_int, [vp, vp, u32]),
+        "rxg_rx_opt_current": (C.c_int, [vp, C.POINTER(vp)]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -591,6 +615,18 @@ def reset_set_id(frame64, ip_id: int) -> bytes:
     buf = C.create_string_buffer(bytes(frame64), len(frame64))
     lib.rxg_reset_set_id(C.addressof(buf), ip_id & 0xFFFF)
     return buf.raw[:64]
+
+
+def rx_opt_parse(frame: bytes) -> np.ndarray:
+    """rxg_rx_opt_parse: the options of one frame taken as a TCP segment, as a RX_OPT_DTYPE
+    scalar (a 0-d record)."""
+    lib = load_library()
+    o = RxOpt()
+    frame = bytes(frame)
+    rc = lib.rxg_rx_opt_parse(frame if frame else None, len(frame), C.byref(o))
+    if rc:
+        raise RxgError(f"rxg_rx_opt_parse failed ({rc})")
+    return np.frombuffer(bytes(o), dtype=RX_OPT_DTYPE)[0]
 
 
 # -------------------------------------------------------------------------- engine ---
@@ -896,6 +932,26 @@ class Engine:
         rc = _lib.rxg_reset_take(self.ctx, ip_id & 0xFFFF, C.byref(p))
         _check(min(rc, 0), "rxg_reset_take")
         return p.value if rc == 1 else None
+
+    def rx_opts_dev(self, frames: int, lens: int, n: int, recs: int, rec_kind: int, out: int,
+                    off64: int | None = None, slot0: int = 0, stride64: int = 0, stream=None):
+        """rxg_rx_opts_dev: one rxg_rx_opt (RX_OPT_DTYPE) at out + 16 * i for every frame i of the
+        burst whose records are at `recs`; the frames at off64[i] or at slot0 + i * stride64."""
+        b = DevRxOpts(frames, off64, lens, slot0, stride64, n, rec_kind, recs, out)
+        _check(_lib.rxg_rx_opts_dev(self.ctx, C.byref(b), stream), "rxg_rx_opts_dev")
+
+    def rx_opts_attach(self, opts_host: int, n: int):
+        """rxg_rx_opts_attach: a host copy (address) of a rx_opts_dev call's output for the next
+        rx replay; the caller keeps it alive until that replay returns."""
+        _check(_lib.rxg_rx_opts_attach(self.ctx, opts_host, n), "rxg_rx_opts_attach")
+
+    def rx_opt_current(self):
+        """Inside a replay's handler: the RX_OPT_DTYPE record of the packet being replayed (a
+        copy), or None (nothing attached, or no replay runs)."""
+        p = C.c_void_p()
+        rc = _lib.rxg_rx_opt_current(self.ctx, C.byref(p))
+        _check(min(rc, 0), "rxg_rx_opt_current")
+        return np.frombuffer(C.string_at(p.value, 16), dtype=RX_OPT_DTYPE)[0] if rc == 1 else None
 
     def tx_build(self, payload: np.ndarray, flows: np.ndarray, segs: np.ndarray, off64=None, slot0: int = 0,
                  stride64: int = 0, opts=None):

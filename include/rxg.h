@@ -738,6 +738,115 @@ int rxg_reset_attach(rxg_ctx *ctx, void *resets_host, const uint32_t *idx_host, 
 int rxg_reset_take(rxg_ctx *ctx, uint16_t ip_id, void **frame_out);
 
 /* ------------------------------------------------------------------------- */
+/* Received TCP options parsed on the device from a burst's frames and         */
+/* records: what a stack otherwise walks per packet on the rx core to echo a   */
+/* timestamp (the tsecr of rxg_tx_opt_timestamp), to learn a SYN's MSS and     */
+/* window scale, and to find a peer's SACK blocks.  The reference ignores      */
+/* received options (its own ACK sends three, tcp_out.c:255-262); the rule     */
+/* below is rxg's definition.                                                  */
+/*                                                                             */
+/* One rxg_rx_opt per frame of the burst, in packet order: record i belongs to */
+/* frame i (dense, no compaction).                                             */
+/*                                                                             */
+/* Candidates.  Frame i is parsed when its record's verdict is RXG_V_DISPATCH, */
+/* RXG_V_RST_NOPCB or RXG_V_RST_LISTEN_NONSYN (the frames the payload gather   */
+/* takes: the replay may turn an RST into a DISPATCH).  Every other frame gets */
+/* an all-zero record.                                                         */
+/*                                                                             */
+/* Option bytes.  The TCP header is at frame + 34 whatever the IHL             */
+/* (tcp_in.c:42-45).  d = frame[46] >> 4.  d < 5: O = 0, RXG_O_BAD_DOFF is set */
+/* and nothing is walked; otherwise O = 4 * d - 20 (0 .. 40).  The option      */
+/* bytes are b[j] = frame[54 + j], j < O.  A byte at or beyond len[i] reads as */
+/* zero (frame[46] too), as the rx kernel and the reset build read truncated   */
+/* frames; RXG_O_CUT (54 + O > len[i]) says that it applied.                   */
+/*                                                                             */
+/* Walk.  p = 0.  While p < O, with k = b[p]:                                  */
+/*   k == 0 (end of option list): stop.                                        */
+/*   k == 1 (no-operation): p += 1, continue.                                  */
+/*   p + 1 >= O (no length byte): RXG_O_MALFORMED, stop.                       */
+/*   l = b[p + 1]; l < 2 or p + l > O: RXG_O_MALFORMED, stop.                  */
+/*   (k, l) = (2, 4)   mss = b[p+2] << 8 | b[p+3], RXG_O_MSS                   */
+/*            (3, 3)   wscale = b[p+2] as it stands (not clamped), _WSCALE     */
+/*            (4, 2)   RXG_O_SACK_PERM                                         */
+/*            (5, 10 / 18 / 26 / 34)  nsack = (l - 2) / 8, sack_off = 54 + p + */
+/*                     2, RXG_O_SACK: the blocks (pairs of big-endian left and */
+/*                     right edges) stay in the frame, at frame + sack_off     */
+/*            (8, 10)  tsval = b[p+2..p+6), tsecr = b[p+6..p+10), both         */
+/*                     big-endian on the wire, host order here, RXG_O_TS       */
+/*            anything else: RXG_O_OTHER (another kind, or a known kind with   */
+/*                     another length), the option is skipped                  */
+/*   p += l.                                                                   */
+/* A later occurrence of a kind replaces an earlier one.  What was found       */
+/* before a RXG_O_MALFORMED stop is kept.  opt_len = O.  The record reports    */
+/* what the header holds: whether an option is legal on this segment (an MSS   */
+/* outside a SYN) is the stack's decision, tcp_flags is in the burst's record. */
+/* ------------------------------------------------------------------------- */
+enum rxg_rx_opt_flag {
+    RXG_O_PARSED = 0x0001,    /* the frame was a candidate and was parsed                     */
+    RXG_O_MSS = 0x0002,
+    RXG_O_WSCALE = 0x0004,
+    RXG_O_SACK_PERM = 0x0008,
+    RXG_O_SACK = 0x0010,
+    RXG_O_TS = 0x0020,
+    RXG_O_OTHER = 0x0040,     /* at least one option was skipped                              */
+    RXG_O_MALFORMED = 0x0080, /* the walk was ended by a bad length                           */
+    RXG_O_CUT = 0x0100,       /* 54 + O > len[i]: option bytes past the frame read as zero    */
+    RXG_O_BAD_DOFF = 0x0200   /* data_off >> 4 is below 5: O = 0, nothing walked              */
+};
+
+typedef struct rxg_rx_opt {   /* 16 bytes */
+    uint32_t tsval, tsecr;    /* host order (big-endian on the wire); 0 without RXG_O_TS      */
+    uint16_t mss;             /* host order; 0 without RXG_O_MSS                               */
+    uint8_t  wscale;          /* the shift byte as it stands (not clamped); 0 without _WSCALE   */
+    uint8_t  nsack;           /* 0..4 SACK blocks                                              */
+    uint8_t  sack_off;        /* frame offset of the first block's left edge (56..86); 0 if none:
+                                 the blocks stay in the frame, which the replay's caller holds */
+    uint8_t  opt_len;         /* O                                                             */
+    uint16_t flags;           /* RXG_O_*                                                       */
+} rxg_rx_opt;
+
+/* frames / off64 / len / slot0 / stride64 follow rxg_dev_batch's readability rules (only bytes
+   up to the end of the 64-byte line holding a frame's last byte are read, plus the first 64
+   bytes at `frames`) and rxg_dev_tx_reset's strided form; recs are the burst's n records as the
+   burst wrote them.  The call is a pure function of its arguments: it reads and writes no
+   mirror, does not depend on the last burst of the context and uses no buffer of the context.
+   One launch, asynchronous on `stream`; rxg_config.max_blocks caps its grid, the output does
+   not depend on the grid.
+   -EINVAL: a NULL ctx, b, frames, len, recs or out; a bad rec_kind; frames or out not 16-byte
+   aligned; off64 not 4-, len not 2-byte aligned, recs not 8- (RXG_REC8) or 16-byte aligned;
+   stride64 0 or slot0 + (n - 1) * stride64 over 2^32 - 1 in strided mode.  n == 0 launches
+   nothing and writes nothing.  A group's members are plain contexts for this call. */
+typedef struct rxg_dev_rx_opts {
+    const void *frames;       /* dev: the burst's frame pool                                     */
+    const uint32_t *off64;    /* dev, n entries; NULL = fixed stride (slot0 + i * stride64)      */
+    const uint16_t *len;      /* dev, n entries                                                  */
+    uint32_t slot0, stride64; /* used when off64 == NULL                                         */
+    uint32_t n;
+    uint32_t rec_kind;        /* RXG_REC8 / RXG_REC16 / RXG_REC48                                */
+    const void *recs;         /* dev: the burst's n records, as the burst wrote them             */
+    rxg_rx_opt *out;          /* dev, 16-byte aligned, n records                                 */
+} rxg_dev_rx_opts;
+int rxg_rx_opts_dev(rxg_ctx *ctx, const rxg_dev_rx_opts *b, void *stream);
+
+/* Host form of the rule (no context, no GPU): one frame taken as a TCP segment -- the caller
+   has the verdict -- parsed into *out (RXG_O_PARSED always set).  Reads frame[0 .. len) only.
+   For frames that reach the stack outside a burst's option pass.  -EINVAL: out NULL, or frame
+   NULL with len > 0. */
+int rxg_rx_opt_parse(const uint8_t *frame, uint32_t len, rxg_rx_opt *out);
+
+/* Using the parsed options during the replay.  rxg_rx_opts_attach names a host copy of a
+   rxg_rx_opts_dev call's `out` (n records) for the burst the next rxg_rx_replay call on this
+   context replays; the attachment ends when that replay returns, however it returns.
+   rxg_rx_opt_current is called from a handler (tcpswitch, send_reset, ..) while the replay
+   runs a packet: it sets *out = &opts_host[that packet's index] and returns 1 -- for a packet
+   the replay re-classified too: options do not depend on the TCB mirror, so they never go
+   stale.  It returns 0 outside a replay, with nothing attached, or when n differs from the
+   replayed burst's.  -EINVAL: ctx or out NULL (attach: ctx NULL, or opts_host NULL with
+   n != 0). */
+int rxg_rx_opts_attach(rxg_ctx *ctx, const rxg_rx_opt *opts_host, uint32_t n);
+int rxg_rx_opt_current(rxg_ctx *ctx, const rxg_rx_opt **out);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
