@@ -12,6 +12,7 @@ import txbuild_ref as ref
 
 HDR = ref.HDR
 OPT_LENS = [0, 4, 8, 12, 16, 28, 40]
+ALL_OPT_LENS = list(range(0, 44, 4))  # every length a block may have (tests/txbuild_opt_cases.py)
 
 
 def opt_len(segs, opts, nopts=None):
