@@ -366,7 +366,9 @@ int rxg_rx_burst_dev(rxg_ctx *ctx, const rxg_dev_batch *b, void *stream);
    calls with no mirror writes between them; one launch (per 32 bursts) instead of k, so the
    launch ramp is paid once.  The bursts are then replayed in order, one rxg_rx_replay call
    each (a replay sees the tcbs[] writes of the earlier bursts' replays), and
-   rxg_payload_gather_dev gathers the burst to be replayed next.  Asynchronous on `stream`. */
+   rxg_payload_gather_dev gathers the burst to be replayed next.  A burst with n == 0 may carry
+   NULL pointers: it is skipped before any pointer is checked or read, and a call whose bursts
+   are all empty launches nothing and returns 0.  Asynchronous on `stream`. */
 typedef struct rxg_dev_burst {
     const uint32_t *off64;  /* dev, n entries, in 64-byte units of the frame pool */
     const uint16_t *len;    /* dev, n entries */
