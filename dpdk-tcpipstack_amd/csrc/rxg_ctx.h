@@ -88,6 +88,7 @@ struct rxg_ctx {
     uint32_t grid_txbo = 0;         // rxg_tx_build_opt_dev's
     uint32_t grid_txr = 0;          // rxg_tx_reset_dev's (its build pass)
     uint32_t grid_rxo = 0;          // rxg_rx_opts_dev's
+    uint32_t grid_txp = 0;          // rxg_tx_plan_dev's (its expand pass)
     // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
     uint32_t grid[2][4] = {};
     rxg::PackPool pack_pool;  // rxg_rx_burst's packing threads
@@ -167,6 +168,9 @@ struct rxg_ctx {
     // call on another stream after the previous call's use of them (recorded after every call)
     DevBuf d_rst_counts;
     hipEvent_t rst_ev = nullptr;
+    // rxg_tx_plan_dev: the tile sums its launches share, under the same rule (txp_ev)
+    DevBuf d_txp_tiles;
+    hipEvent_t txp_ev = nullptr;
     // rxg_reset_attach: host copies of a call's resets and their packet indices for the replay
     // that follows (cleared when it returns), and rxg_reset_take's cursor into them
     uint8_t *rst_host = nullptr;

@@ -87,6 +87,7 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         c->grid_txbo = cus * (uint32_t)tx_build_blocks_per_cu(true);  // rxg_tx_build_opt_dev's
         c->grid_txr = cus * (uint32_t)tx_reset_blocks_per_cu();  // rxg_tx_reset_dev's
         c->grid_rxo = cus * (uint32_t)rx_opts_blocks_per_cu();  // rxg_rx_opts_dev's
+        c->grid_txp = cus * (uint32_t)tx_plan_blocks_per_cu();  // rxg_tx_plan_dev's
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -165,9 +166,10 @@ extern "C" int rxg_fini(rxg_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->tables.wait_readers(true);  // table readers still running on caller streams
     for (DevBuf *b : {&c->tables.buckets, &c->tables.listen, &c->d_sel, &c->d_fix, &c->tables.d_arp, &c->d_pg_status,
-                      &c->d_pg_ticket, &c->d_soff, &c->d_rst_counts})
+                      &c->d_pg_ticket, &c->d_soff, &c->d_rst_counts, &c->d_txp_tiles})
         if (b->p) (void)hipFree(b->p);
     if (c->rst_ev) (void)hipEventDestroy(c->rst_ev);
+    if (c->txp_ev) (void)hipEventDestroy(c->txp_ev);
     if (c->h_pm) (void)hipHostFree(c->h_pm);
     if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
     c->tables.destroy();
@@ -815,6 +817,55 @@ extern "C" int rxg_tx_reset_dev(rxg_ctx *c, const rxg_dev_tx_reset *b, void *str
     const hipError_t e = launch_tx_reset(L, st);
     // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
     if (b->n) HIP_OK(hipEventRecord(c->rst_ev, st));
+    HIP_OK(e);
+    return 0;
+}
+
+static_assert(sizeof(rxg_tx_send) == 40 && sizeof(rxg_dev_tx_plan) == 80, "device planner layouts");
+
+extern "C" int rxg_tx_plan_dev(rxg_ctx *c, const rxg_dev_tx_plan *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_tx_plan_dev: NULL argument");
+    if (!b->sends || !b->first || !b->count || (!b->segs && b->cap))
+        return fail(-EINVAL, "rxg_tx_plan_dev: NULL device pointer");
+    if (((uintptr_t)b->sends & 7u) || ((uintptr_t)b->segs & 7u) || ((uintptr_t)b->first & 7u) ||
+        ((uintptr_t)b->count & 7u) || ((uintptr_t)b->opts & 15u) || ((uintptr_t)b->next_seq & 3u) ||
+        ((uintptr_t)b->send_opt & 3u))
+        return fail(-EINVAL, "rxg_tx_plan_dev: sends, segs, first and count need 8-byte, opts 16-byte, next_seq and "
+                             "send_opt 4-byte alignment");
+    if (b->mss == 0 || b->mss > RXG_TX_MAX_DATA) return fail(-EINVAL, "rxg_tx_plan_dev: mss %u", b->mss);
+    if (!b->opts && b->nopts) return fail(-EINVAL, "rxg_tx_plan_dev: NULL opts with nopts %u", b->nopts);
+    int rc = set_device(c);
+    if (rc) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchTxPlan L;
+    L.sends = b->sends;
+    L.nsends = b->nsends;
+    L.mss = b->mss;
+    L.send_opt = b->send_opt;
+    L.opts = b->opts;
+    L.nopts = b->nopts;
+    L.segs = b->segs;
+    L.cap = b->cap;
+    L.first = (unsigned long long *)b->first;
+    L.next_seq = b->next_seq;
+    L.count = (unsigned long long *)b->count;
+    L.tiles = nullptr;
+    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txp ? c->grid_txp : 1024u);  // (as grid_for)
+    if (b->nsends) {
+        // One call at a time uses the context's tile sums (rxg_tx_reset_dev's rule): a call
+        // waits, on its stream, for the previous call's last launch (txp_ev); before the buffer
+        // is replaced for more sends the host waits for that launch instead.
+        const size_t need = tx_plan_tile_bytes(b->nsends);
+        if (c->txp_ev && c->d_txp_tiles.bytes < need) HIP_OK(hipEventSynchronize(c->txp_ev));
+        if ((rc = ensure(c->d_txp_tiles, need))) return rc;
+        if (c->txp_ev) HIP_OK(hipStreamWaitEvent(st, c->txp_ev, 0));
+        else HIP_OK(hipEventCreateWithFlags(&c->txp_ev, hipEventDisableTiming));
+        L.tiles = c->d_txp_tiles.p;
+    }
+    const hipError_t e = launch_tx_plan(L, st);
+    // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
+    if (b->nsends) HIP_OK(hipEventRecord(c->txp_ev, st));
     HIP_OK(e);
     return 0;
 }

@@ -200,6 +200,26 @@ struct LaunchTxReset {
 hipError_t launch_tx_reset(const LaunchTxReset &R, hipStream_t st);
 size_t tx_reset_count_bytes(uint32_t n);  // the slice-count buffer a call of n frames needs
 int tx_reset_blocks_per_cu();  // resident 256-thread workgroups per CU of the build pass
+// rxg_txplan.hip: sends cut into segment descriptors (rxg_tx_plan_dev): a count pass, a
+// one-workgroup scan, an offsets pass and an expand pass on `st` (nsends == 0: count = {0, 0}
+// and first[0] = 0 only)
+struct LaunchTxPlan {
+    const rxg_tx_send *sends;
+    uint32_t nsends, mss;
+    const uint32_t *send_opt;   // nullptr: no send names a block
+    const rxg_tx_opt *opts;     // nopts blocks, or nullptr with nopts 0
+    uint32_t nopts;
+    rxg_tx_seg *segs;
+    unsigned long long cap;
+    unsigned long long *first;  // nsends + 1 entries
+    uint32_t *next_seq;         // may be nullptr
+    unsigned long long *count;  // {total, refused sends}
+    void *tiles;                // tx_plan_tile_bytes(nsends) bytes, shared by the launches
+    uint32_t max_blocks;        // grid cap of the count, offsets and expand passes; 0 = 2^16
+};
+hipError_t launch_tx_plan(const LaunchTxPlan &P, hipStream_t st);
+size_t tx_plan_tile_bytes(uint32_t nsends);  // the tile buffer a call of nsends sends needs
+int tx_plan_blocks_per_cu();  // resident 256-thread workgroups per CU of the expand pass
 // rxg_rxopt.hip: the TCP options of a burst's segments (rxg_rx_opts_dev), one launch on `st`
 // (n == 0: none)
 struct LaunchRxOpts {

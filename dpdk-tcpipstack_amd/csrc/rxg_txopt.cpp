@@ -1,6 +1,7 @@
 // rxg_txopt.cpp — the host side of TCP option blocks (rxg_tx_build_opt_dev's table entries):
 // rxg_tx_opt_set / _timestamp / _ref_ack fill a block, rxg_tx_plan_opt cuts sends whose
-// segments carry one.  Pure host code (rxg.h, rxg_tx_plan and libc only: it compiles
+// segments carry one, rxg_tx_plan_count counts the segments of such a cut (the `n` of the build
+// that follows rxg_tx_plan_dev).  Pure host code (rxg.h, rxg_tx_plan and libc only: it compiles
 // stand-alone with rxg_txplan.cpp).
 #include <errno.h>
 #include <stddef.h>
@@ -44,6 +45,26 @@ extern "C" int rxg_tx_opt_ref_ack(rxg_tx_opt *o)
                                   2, 4, 0x05, 0x14,                           // htons(1300), tcp_out.c:20-27
                                   3, 3, 7};                                   // tcp_out.c:29-36
     return rxg_tx_opt_set(o, b, sizeof b);  // + 3 bytes of pad (tcp_out.c:258-262)
+}
+
+extern "C" int64_t rxg_tx_plan_count(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss,
+                                     const uint32_t *send_opt, const rxg_tx_opt *opts, uint32_t nopts)
+{
+    if (mss == 0 || mss > RXG_TX_MAX_DATA) return -EINVAL;
+    if (nsends && !sends) return -EINVAL;
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < nsends; ++j) {
+        uint32_t O = 0;
+        if (send_opt && send_opt[j]) {  // the planner's checks of a named block
+            const uint32_t k = send_opt[j];
+            if (k > nopts || !opts) return -EINVAL;
+            O = opts[k - 1u].len;
+            if (O > 40u || (O & 3u) || mss <= O) return -EINVAL;
+        }
+        const uint32_t m = mss - O;
+        total += sends[j].bytes ? ((uint64_t)sends[j].bytes + m - 1u) / m : 1u;
+    }
+    return (int64_t)total;
 }
 
 extern "C" int64_t rxg_tx_plan_opt(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss, const uint32_t *send_opt,

@@ -241,6 +241,13 @@ class DevTxBuildOpt(C.Structure):
     _fields_ = [("b", DevTxBuild), ("opts", C.c_void_p), ("nopts", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class DevTxPlan(C.Structure):
+    """rxg_dev_tx_plan."""
+    _fields_ = [("sends", C.c_void_p), ("nsends", C.c_uint32), ("mss", C.c_uint32), ("send_opt", C.c_void_p),
+                ("opts", C.c_void_p), ("nopts", C.c_uint32), ("pad", C.c_uint32), ("segs", C.c_void_p),
+                ("cap", C.c_uint64), ("first", C.c_void_p), ("next_seq", C.c_void_p), ("count", C.c_void_p)]
+
+
 class DevTxReset(C.Structure):
     """rxg_dev_tx_reset."""
     _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
@@ -377,6 +384,8 @@ def load_library(path: str = LIB_PATH):
         "rxg_tx_opt_timestamp": (C.c_int, [vp, u32, u32]),
         "rxg_tx_opt_ref_ack": (C.c_int, [vp]),
         "rxg_tx_plan_opt": (C.c_int64, [vp, u32, u32, vp, vp, u32, vp, u64, vp]),
+        "rxg_tx_plan_count": (C.c_int64, [vp, u32, u32, vp, vp, u32]),
+        "rxg_tx_plan_dev": (C.c_int, [vp, C.POINTER(DevTxPlan), vp]),
         "rxg_tx_reset_dev": (C.c_int, [vp, C.POINTER(DevTxReset), vp]),
         "rxg_reset_set_id": (None, [vp, C.c_uint16]),
         "rxg_reset_attach": (C.c_int, [vp, vp, vp, u64]),
@@ -599,6 +608,23 @@ def tx_plan_opt(sends, mss: int, send_opt, opts):
     if rc < 0:
         raise RxgError(f"rxg_tx_plan_opt failed ({rc})")
     return segs[:rc].copy(), nxt
+
+
+def tx_plan_count(sends, mss: int, send_opt=None, opts=None) -> int:
+    """rxg_tx_plan_count: the number of segments tx_plan_opt(sends, mss, send_opt, opts) (send_opt
+    None: tx_plan) would write, without writing them: the n of the build that follows
+    Engine.tx_plan_dev.  sends: TX_SEND_DTYPE."""
+    lib = load_library()
+    sends = np.ascontiguousarray(sends, dtype=TX_SEND_DTYPE)
+    so = None if send_opt is None else np.ascontiguousarray(send_opt, dtype=np.uint32)
+    if so is not None and len(so) != len(sends):
+        raise ValueError("tx_plan_count: one send_opt entry per send")
+    ob = np.zeros(0, dtype=TX_OPT_DTYPE) if opts is None else np.ascontiguousarray(opts, dtype=TX_OPT_DTYPE).reshape(-1)
+    rc = lib.rxg_tx_plan_count(_ptr(sends) if len(sends) else None, len(sends), mss & 0xFFFFFFFF,
+                               None if so is None else _ptr(so), _ptr(ob) if len(ob) else None, len(ob))
+    if rc < 0:
+        raise RxgError(f"rxg_tx_plan_count failed ({rc})")
+    return int(rc)
 
 
 def reset_set_id(frame64, ip_id: int) -> bytes:
@@ -909,6 +935,17 @@ class Engine:
         b = DevTxBuildOpt(DevTxBuild(payload, payload_bytes, flows, nflows, n, segs, frames, off64, slot0, stride64,
                                      lens, stats), opts, nopts, 0)
         _check(_lib.rxg_tx_build_opt_dev(self.ctx, C.byref(b), stream), "rxg_tx_build_opt_dev")
+
+    def tx_plan_dev(self, sends: int, nsends: int, mss: int, segs: int | None, cap: int, first: int, count: int,
+                    send_opt: int | None = None, opts: int | None = None, nopts: int = 0,
+                    next_seq: int | None = None, stream=None):
+        """rxg_tx_plan_dev: the nsends rxg_tx_send at `sends` cut into rxg_tx_seg at `segs` (at most
+        cap of them), first[j] = the index of send j's first segment (nsends + 1 entries),
+        next_seq[j] the sequence number after send j, count = {segments the sends need, refused
+        sends}; send j carries block send_opt[j] (0: none, k: the k-th rxg_tx_opt at `opts`).  All
+        device addresses."""
+        b = DevTxPlan(sends, nsends, mss, send_opt, opts, nopts, 0, segs, cap, first, next_seq, count)
+        _check(_lib.rxg_tx_plan_dev(self.ctx, C.byref(b), stream), "rxg_tx_plan_dev")
 
     def tx_reset_dev(self, frames: int, lens: int, n: int, recs: int, rec_kind: int, out: int, idx: int, cap: int,
                      count: int, off64: int | None = None, slot0: int = 0, stride64: int = 0, ip_id0: int = 0,

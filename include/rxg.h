@@ -656,6 +656,70 @@ int64_t rxg_tx_plan_opt(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss,
                         const rxg_tx_opt *opts, uint32_t nopts, rxg_tx_seg *out, uint64_t cap,
                         uint32_t *next_seq_out);
 
+/* The number of segments rxg_tx_plan_opt would write for these sends (send_opt NULL:
+   rxg_tx_plan), with its -EINVAL cases (those about out and cap apart), writing nothing: the
+   `n` of the build launch that follows rxg_tx_plan_dev, known to the caller who made the
+   sends without a device-to-host wait.  Host, no context, no GPU. */
+int64_t rxg_tx_plan_count(const rxg_tx_send *sends, uint32_t nsends, uint32_t mss, const uint32_t *send_opt,
+                          const rxg_tx_opt *opts, uint32_t nopts);
+
+/* ------------------------------------------------------------------------- */
+/* Transmit segment plan on the device: rxg_tx_plan_opt's cut of sends into    */
+/* segment descriptors, with the sends as the only thing that crosses to the   */
+/* device: "sends in, frames out" with rxg_tx_build_dev / _opt_dev after it.   */
+/*                                                                             */
+/* Let O_j be the len of the block send j names (send_opt[j] = k: opts[k - 1]; */
+/* 0 when k is 0 or send_opt is NULL) and m_j = mss - O_j.  Send j has nseg_j  */
+/* = ceil(bytes / m_j) segments, one when bytes is 0.  first[j] is the sum of  */
+/* nseg over the sends before j, first[nsends] = the total = count[0].         */
+/* Segment q of send j is segs[first[j] + q]:                                  */
+/*   src_off    send.src_off + q * m_j (64-bit)                                */
+/*   flow, ack, win_raw   the send's                                           */
+/*   data_len   m_j, the last segment bytes - (nseg_j - 1) * m_j               */
+/*   seq        next_seq + q * m_j (mod 2^32), + 1 when q > 0 and the send     */
+/*              carries SYN (tcp_out.c:176-185)                                */
+/*   ip_id      (uint16_t)(ip_id0 + q)                                         */
+/*   tcp_flags  SYN on segment 0 only, FIN and PSH on the last only, every     */
+/*              other flag on all                                              */
+/*   pad 0;  reserved = send_opt[j] (0 when send_opt is NULL)                  */
+/* next_seq[j] = next_seq + bytes (mod 2^32), + 1 for SYN, + 1 for FIN.        */
+/* When no send is refused and total <= cap this is rxg_tx_plan_opt's output   */
+/* in all 32 bytes of every descriptor, and its next_seq_out; only then.       */
+/*                                                                             */
+/* Where the call differs from the host planner, which returns an error about  */
+/* data this call has not read when it returns:                                */
+/*   Refused sends.  A send is refused when send_opt[j] > nopts, when its      */
+/*   block's len is over 40 or not a multiple of 4, or when mss <= O_j.  It    */
+/*   gets no segments (first[j + 1] == first[j]), next_seq[j] is its next_seq  */
+/*   unchanged and count[1] counts it.  A block is read only once send_opt[j]  */
+/*   <= nopts is established.                                                  */
+/*   Cap.  Segments with index >= cap are not written; count[0] and first[]    */
+/*   still hold what the sends need (rxg_tx_reset_dev's cap / *count rule).    */
+/* src_off is never followed, flow indices are not checked: the build does.    */
+/* -EINVAL: a NULL ctx, b, sends, first or count; segs NULL with cap != 0;     */
+/* sends, segs, first or count not 8-, opts not 16-, next_seq or send_opt not  */
+/* 4-byte aligned; mss 0 or over RXG_TX_MAX_DATA; opts NULL with nopts != 0.   */
+/* nsends == 0 writes count = {0, 0} and first[0] = 0, and nothing else.       */
+/* Asynchronous on `stream`; a pure function of its arguments: it reads and    */
+/* writes no mirror.  The context owns a small device buffer of per-tile sums  */
+/* that all calls share: a call on another stream waits (on the device,        */
+/* through an event) for the previous call on this context.                    */
+/* ------------------------------------------------------------------------- */
+typedef struct rxg_dev_tx_plan {
+    const rxg_tx_send *sends;  /* dev, 8-byte aligned, nsends entries (40 bytes each)            */
+    uint32_t nsends, mss;
+    const uint32_t *send_opt;  /* dev, nsends entries, or NULL: no send carries a block          */
+    const rxg_tx_opt *opts;    /* dev, 16-byte aligned; may be NULL when nopts == 0              */
+    uint32_t nopts, pad;
+    rxg_tx_seg *segs;          /* dev, 8-byte aligned, WRITTEN: segments 0 .. min(total, cap)    */
+    uint64_t cap;              /* entries in segs                                                */
+    uint64_t *first;           /* dev, nsends + 1 entries, WRITTEN: first[j] = index of send j's
+                                  first segment, first[nsends] = total                           */
+    uint32_t *next_seq;        /* dev, nsends entries, WRITTEN; may be NULL                      */
+    uint64_t *count;           /* dev, 2 words, WRITTEN (not added to): {total, refused sends}   */
+} rxg_dev_tx_plan;
+int rxg_tx_plan_dev(rxg_ctx *ctx, const rxg_dev_tx_plan *b, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* Reset replies built on the device from a burst's records: what send_reset   */
 /* -> ip_out -> ether_out do per offending packet (tcp_out.c:103-146,          */
