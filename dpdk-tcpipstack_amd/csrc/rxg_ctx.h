@@ -181,6 +181,16 @@ struct rxg_ctx {
     const rxg_rx_opt *opt_host = nullptr;
     uint32_t opt_n = 0;
     bool opt_live = false;  // the running replay's burst has opt_n frames
+    // rxg_flow_sums_dev: the dense accumulator and the touched bitmap (all zero between calls),
+    // the tile counts, and the event that orders a call after the previous one (rst_ev's rule)
+    DevBuf d_fs_acc, d_fs_bits, d_fs_tiles;
+    hipEvent_t fs_ev = nullptr;
+    bool fs_dirty = false;  // a launch failed part-way: both are zeroed again before the next
+    uint32_t grid_fs = 0;   // its accumulation's grid (set at init)
+    // rxg_flow_sums_attach: a host copy of a call's summaries for the replay that follows
+    // (cleared when it returns); rxg_flow_sum_current answers from it
+    const rxg_flow_sum *fs_host = nullptr;
+    uint64_t fs_m = 0;
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;

@@ -88,6 +88,10 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         c->grid_txr = cus * (uint32_t)tx_reset_blocks_per_cu();  // rxg_tx_reset_dev's
         c->grid_rxo = cus * (uint32_t)rx_opts_blocks_per_cu();  // rxg_rx_opts_dev's
         c->grid_txp = cus * (uint32_t)tx_plan_blocks_per_cu();  // rxg_tx_plan_dev's
+        // rxg_flow_sums_dev's accumulation: one workgroup per CU.  Every workgroup ends with one
+        // set of atomics on its carried flow, and atomics on one line run one after the other:
+        // 256 workgroups measured faster than 1 024 on every shape
+        c->grid_fs = cus;
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -166,10 +170,12 @@ extern "C" int rxg_fini(rxg_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->tables.wait_readers(true);  // table readers still running on caller streams
     for (DevBuf *b : {&c->tables.buckets, &c->tables.listen, &c->d_sel, &c->d_fix, &c->tables.d_arp, &c->d_pg_status,
-                      &c->d_pg_ticket, &c->d_soff, &c->d_rst_counts, &c->d_txp_tiles})
+                      &c->d_pg_ticket, &c->d_soff, &c->d_rst_counts, &c->d_txp_tiles, &c->d_fs_acc,
+                      &c->d_fs_bits, &c->d_fs_tiles})
         if (b->p) (void)hipFree(b->p);
     if (c->rst_ev) (void)hipEventDestroy(c->rst_ev);
     if (c->txp_ev) (void)hipEventDestroy(c->txp_ev);
+    if (c->fs_ev) (void)hipEventDestroy(c->fs_ev);
     if (c->h_pm) (void)hipHostFree(c->h_pm);
     if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
     c->tables.destroy();
@@ -902,6 +908,96 @@ extern "C" int rxg_rx_opts_dev(rxg_ctx *c, const rxg_dev_rx_opts *b, void *strea
     L.out = (uint8_t *)b->out;
     L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_rxo ? c->grid_rxo : 1024u);  // (as grid_for)
     HIP_OK(launch_rx_opts(L, pick(c, stream)));
+    return 0;
+}
+
+static_assert(sizeof(rxg_flow_sum) == 40 && sizeof(rxg_dev_flow_sums) == 80, "flow summary layouts");
+
+// b grown to `bytes` (never shrunk) for rxg_flow_sums_dev.  zero: the new memory is zeroed on
+// st -- the old held nothing but zeroes once the previous call was done, which the host waits
+// for before the buffer is replaced.  -ENOMEM when it cannot be had (b is then empty).
+static int fs_grow(rxg_ctx *c, DevBuf &b, size_t bytes, bool zero, hipStream_t st)
+{
+    if (b.p && b.bytes >= bytes) return 0;
+    if (c->fs_ev) HIP_OK(hipEventSynchronize(c->fs_ev));
+    if (b.p) HIP_OK(hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    const size_t want = std::max<size_t>(bytes, 256);
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return fail(-ENOMEM, "rxg_flow_sums_dev: %zu bytes of device memory", want);
+    }
+    b.bytes = want;
+    if (zero) HIP_OK(hipMemsetAsync(b.p, 0, want, st));
+    return 0;
+}
+
+extern "C" int rxg_flow_sums_dev(rxg_ctx *c, const rxg_dev_flow_sums *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_flow_sums_dev: NULL argument");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_flow_sums_dev: rec_kind %u", b->rec_kind);
+    const bool reads_frames = b->rec_kind != RXG_REC48;
+    if (!b->recs || !b->count || (!b->out && b->cap) || (reads_frames && (!b->frames || !b->len)))
+        return fail(-EINVAL, "rxg_flow_sums_dev: NULL device pointer");
+    if (b->ntcb == 0 || b->ntcb > RXG_FS_MAX_NTCB) return fail(-EINVAL, "rxg_flow_sums_dev: ntcb %u", b->ntcb);
+    if (b->flags & ~RXG_FS_TCP_OK_ONLY) return fail(-EINVAL, "rxg_flow_sums_dev: unknown flags 0x%x", b->flags);
+    const uintptr_t rec_align = b->rec_kind == RXG_REC8 ? 8u : 16u;  // (as rxg_rx_burst_dev)
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 7u) || ((uintptr_t)b->count & 7u) ||
+        ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align - 1u)))
+        return fail(-EINVAL, "rxg_flow_sums_dev: frames need 16-byte, out and count 8-byte, off64 4-byte, len 2-byte, "
+                             "recs %u-byte alignment", (unsigned)rec_align);
+    if (reads_frames && !b->off64) {
+        if (!b->stride64) return fail(-EINVAL, "rxg_flow_sums_dev: stride64 0");
+        if (b->n && (uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
+            return fail(-EINVAL, "rxg_flow_sums_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchFlowSum L;
+    L.frames = reads_frames ? (const uint8_t *)b->frames : nullptr;
+    L.off64 = b->off64;
+    L.len = b->len;
+    L.slot0 = b->slot0;
+    L.stride64 = b->stride64;
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.ntcb = b->ntcb;
+    L.flags = b->flags;
+    L.out = b->out;
+    L.cap = b->cap;
+    L.count = (unsigned long long *)b->count;
+    L.acc = nullptr;
+    L.bits = nullptr;
+    L.tiles = nullptr;
+    L.max_blocks = c->max_blocks;
+    L.acc_blocks = c->grid_fs ? c->grid_fs : 1024u;
+    if (b->n) {
+        // One call at a time uses the context's accumulator, bitmap and tile counts
+        // (rxg_tx_reset_dev's rule): a call waits, on its stream, for the previous call's last
+        // launch (fs_ev); before a buffer is replaced for a larger ntcb the host waits instead.
+        if ((rc = fs_grow(c, c->d_fs_acc, flow_sum_bytes(b->ntcb), true, st))) return rc;
+        if ((rc = fs_grow(c, c->d_fs_bits, flow_sum_bits_bytes(b->ntcb), true, st))) return rc;
+        if ((rc = fs_grow(c, c->d_fs_tiles, flow_sum_tile_bytes(b->ntcb), false, st))) return rc;
+        if (c->fs_ev) HIP_OK(hipStreamWaitEvent(st, c->fs_ev, 0));
+        else HIP_OK(hipEventCreateWithFlags(&c->fs_ev, hipEventDisableTiming));
+        if (c->fs_dirty) {
+            HIP_OK(hipMemsetAsync(c->d_fs_acc.p, 0, c->d_fs_acc.bytes, st));
+            HIP_OK(hipMemsetAsync(c->d_fs_bits.p, 0, c->d_fs_bits.bytes, st));
+            c->fs_dirty = false;
+        }
+        L.acc = (FlowSumAcc *)c->d_fs_acc.p;
+        L.bits = (uint32_t *)c->d_fs_bits.p;
+        L.tiles = (uint32_t *)c->d_fs_tiles.p;
+    }
+    const hipError_t e = launch_flow_sum(L, st);
+    if (b->n && e != hipSuccess) c->fs_dirty = true;
+    // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
+    if (b->n) HIP_OK(hipEventRecord(c->fs_ev, st));
+    HIP_OK(e);
     return 0;
 }
 

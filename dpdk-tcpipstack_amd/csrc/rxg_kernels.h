@@ -235,6 +235,43 @@ struct LaunchRxOpts {
 };
 hipError_t launch_rx_opts(const LaunchRxOpts &R, hipStream_t st);
 int rx_opts_blocks_per_cu();  // resident 256-thread workgroups per CU of its kernel
+// rxg_flowsum.hip: a burst summarised per flow (rxg_flow_sums_dev): the accumulation, the
+// touched bitmap's per-tile counts, their one-workgroup scan and the expansion on `st`
+// (n == 0: count = {0, 0, 0} only)
+struct FlowSumAcc {         // one accumulator entry; all zero between calls
+    uint32_t frames, max_seq, max_ack;
+    uint32_t first_enc;     // max of ~i over the counted frames (0: none)
+    uint32_t last_enc;      // max of i + 1
+    uint32_t data_frames, flags_or, pad;
+    unsigned long long data_bytes;
+};
+static_assert(sizeof(FlowSumAcc) == 40, "accumulator entry");
+constexpr uint32_t kFsTileWords = 64;                  // bitmap words per count tile (one per lane)
+constexpr uint32_t kFsTileTcbs = kFsTileWords * 32u;   // TCBs per count tile
+constexpr uint32_t kFsScanLanes = 1024;                // tiles per round of the scan
+struct LaunchFlowSum {
+    const uint8_t *frames;  // may be nullptr for RXG_REC48
+    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
+    const uint16_t *len;
+    uint32_t slot0, stride64;
+    uint32_t n;
+    uint32_t rec_kind;
+    const uint8_t *recs;
+    uint32_t ntcb, flags;
+    rxg_flow_sum *out;
+    unsigned long long cap;
+    unsigned long long *count;  // 3 words
+    FlowSumAcc *acc;            // flow_sum_bytes(ntcb) bytes, all zero
+    uint32_t *bits;             // flow_sum_bits_bytes(ntcb) bytes, all zero: two 64-bit words of
+                                // left-out frames (count[1], count[2]), then the touched bitmap
+    uint32_t *tiles;            // flow_sum_tile_bytes(ntcb) bytes, any content
+    uint32_t max_blocks;        // grid cap of the count and expand passes; 0 = none
+    uint32_t acc_blocks;        // grid of the accumulation (its waves carry a flow across slices)
+};
+hipError_t launch_flow_sum(const LaunchFlowSum &F, hipStream_t st);
+size_t flow_sum_bytes(uint32_t ntcb);
+size_t flow_sum_bits_bytes(uint32_t ntcb);
+size_t flow_sum_tile_bytes(uint32_t ntcb);
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

@@ -192,6 +192,37 @@ extern "C" int rxg_rx_opt_current(rxg_ctx *c, const rxg_rx_opt **out)
     return 1;
 }
 
+// ---------------------------------------------------------------- flow summaries ---
+extern "C" int rxg_flow_sums_attach(rxg_ctx *c, const rxg_flow_sum *sums_host, uint64_t m)
+{
+    if (!c || (m && !sums_host)) return fail(-EINVAL, "rxg_flow_sums_attach: NULL argument");
+    for (uint64_t k = 1; k < m; ++k)
+        if (sums_host[k].tcb_idx <= sums_host[k - 1].tcb_idx)
+            return fail(-EINVAL, "rxg_flow_sums_attach: entry %llu is not above its predecessor's tcb_idx",
+                        (unsigned long long)k);
+    c->fs_host = m ? sums_host : nullptr;
+    c->fs_m = m;
+    return 0;
+}
+
+// The packet being replayed, if its record is still the burst's (rp_seq 0: not re-classified)
+// and a DISPATCH to a flow of the attached list that covers its index.
+extern "C" int rxg_flow_sum_current(rxg_ctx *c, const rxg_flow_sum **out, uint32_t *pkt_idx)
+{
+    if (!c || !out || !pkt_idx) return fail(-EINVAL, "rxg_flow_sum_current: NULL argument");
+    const int64_t pos = c->replay_pos;
+    if (pos < 0 || !c->fs_host || (uint64_t)pos >= c->rp_cur.size() || (uint64_t)pos >= c->rp_seq.size()) return 0;
+    const rxg_rec16 &r = c->rp_cur[(size_t)pos];
+    if (c->rp_seq[(size_t)pos] != 0u || r.verdict != RXG_V_DISPATCH) return 0;
+    const rxg_flow_sum *lo = c->fs_host, *hi = c->fs_host + c->fs_m;
+    const rxg_flow_sum *s =
+        std::lower_bound(lo, hi, r.tcb_idx, [](const rxg_flow_sum &e, int32_t t) { return e.tcb_idx < t; });
+    if (s == hi || s->tcb_idx != r.tcb_idx || (uint64_t)pos < s->first_idx || (uint64_t)pos > s->last_idx) return 0;
+    *out = s;
+    *pkt_idx = (uint32_t)pos;
+    return 1;
+}
+
 // ------------------------------------------------------------------------- replay ---
 static inline bool rec_is_tcp(const rxg_rec16 &r)
 {
@@ -307,6 +338,8 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
             c->opt_host = nullptr;
             c->opt_n = 0;
             c->opt_live = false;
+            c->fs_host = nullptr;
+            c->fs_m = 0;
         }
     } pos_guard{c};
     if (!ops || (n && (!mbufs || !frames || !recs)))

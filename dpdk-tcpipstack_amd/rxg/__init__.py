@@ -10,6 +10,7 @@ The reference surface this mirrors (rajneshrat/dpdk-tcpipstack, tcp_ip_stack/):
   ip_out's two checksums (ip.c:97-118)        -> Engine.tx_cksum_dev
   send_reset per offender (tcp_out.c:103-146) -> Engine.tx_reset_dev, reset_attach / reset_take
   (no counterpart: received TCP options)     -> Engine.rx_opts_dev, rx_opt_parse, rx_opts_attach / rx_opt_current
+  on_segment's per-flow work (tcp_in.c:66-71) -> Engine.flow_sums_dev, flow_sums_host, flow_sums_attach / flow_sum_current
 """
 from __future__ import annotations
 
@@ -108,6 +109,17 @@ RX_OPT_DTYPE = np.dtype([("tsval", "<u4"), ("tsecr", "<u4"), ("mss", "<u2"), ("w
 assert RX_OPT_DTYPE.itemsize == 16
 (O_PARSED, O_MSS, O_WSCALE, O_SACK_PERM, O_SACK, O_TS, O_OTHER, O_MALFORMED, O_CUT,
  O_BAD_DOFF) = (1 << k for k in range(10))
+# a burst summarised per flow (rxg_flow_sums_dev, rxg_flow_sums_host): rxg_flow_sum
+FLOW_SUM_DTYPE = np.dtype([("tcb_idx", "<i4"), ("frames", "<u4"), ("max_seq", "<u4"), ("max_ack", "<u4"),
+                           ("first_idx", "<u4"), ("last_idx", "<u4"), ("data_frames", "<u4"), ("tcp_flags_or", "u1"),
+                           ("state", "u1"), ("reserved", "<u2"), ("data_bytes", "<u8")])
+assert FLOW_SUM_DTYPE.itemsize == 40
+FS_TCP_OK_ONLY = 1
+FS_MAX_NTCB = 1 << 24
+# csrc/rxg_kernels.h kFsTileTcbs / kFsScanLanes: TCBs per count tile of the touched bitmap, tiles
+# per round of the scan (what the edge tests are named from)
+FLOW_SUM_TILE_TCBS = 2048
+FLOW_SUM_SCAN_TILES = 1024
 
 
 def rec8_pack(r16: np.ndarray) -> np.ndarray:
@@ -272,6 +284,14 @@ class DevRxOpts(C.Structure):
                 ("out", C.c_void_p)]
 
 
+class DevFlowSums(C.Structure):
+    """rxg_dev_flow_sums."""
+    _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
+                ("stride64", C.c_uint32), ("n", C.c_uint32), ("rec_kind", C.c_uint32), ("recs", C.c_void_p),
+                ("ntcb", C.c_uint32), ("flags", C.c_uint32), ("out", C.c_void_p), ("cap", C.c_uint64),
+                ("count", C.c_void_p)]
+
+
 class PktView(C.Structure):
     _fields_ = [("buf_addr", C.c_void_p), ("data_off", C.c_uint16), ("data_len", C.c_uint16),
                 ("pad", C.c_uint32)]
@@ -394,6 +414,10 @@ def load_library(path: str = LIB_PATH):
         "rxg_rx_opt_parse": (C.c_int, [C.c_char_p, u32, C.POINTER(RxOpt)]),
         "rxg_rx_opts_attach": (C.c_int, [vp, vp, u32]),
         "rxg_rx_opt_current": (C.c_int, [vp, C.POINTER(vp)]),
+        "rxg_flow_sums_dev": (C.c_int, [vp, C.POINTER(DevFlowSums), vp]),
+        "rxg_flow_sums_host": (C.c_int, [vp, u32, vp, vp, u32, u32, u32, vp, u64, vp]),
+        "rxg_flow_sums_attach": (C.c_int, [vp, vp, u64]),
+        "rxg_flow_sum_current": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u32)]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -653,6 +677,31 @@ def rx_opt_parse(frame: bytes) -> np.ndarray:
     if rc:
         raise RxgError(f"rxg_rx_opt_parse failed ({rc})")
     return np.frombuffer(bytes(o), dtype=RX_OPT_DTYPE)[0]
+
+
+def flow_sums_host(recs, rec_kind: int, ntcb: int, frames=None, flags: int = 0, cap=None, out=None):
+    """rxg_flow_sums_host: the per-flow summaries of a burst in host memory.  recs: the burst's
+    records (an array of REC8_DTYPE / REC16_DTYPE / REC48_DTYPE matching rec_kind); frames: the
+    list of frames as bytes (may be None for REC48).  Returns (sums FLOW_SUM_DTYPE of min(count[0],
+    cap) entries, count u64[3]); cap None: room for every flow.  out: a FLOW_SUM_DTYPE array of at
+    least cap entries written in place (returned whole instead)."""
+    lib = load_library()
+    recs = np.ascontiguousarray(recs)
+    n = recs.nbytes // rec_kind if rec_kind in (REC8, REC16, REC48) else len(recs)
+    keep, ptrs, lens = [], None, None
+    if frames is not None:
+        keep = [C.create_string_buffer(bytes(f), max(len(f), 1)) for f in frames]
+        ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(x) for x in keep])
+        lens = np.array([len(f) for f in frames], np.uint16)
+    if cap is None:
+        cap = n
+    buf = out if out is not None else np.zeros(max(cap, 1), FLOW_SUM_DTYPE)
+    count = np.zeros(3, np.uint64)
+    rc = lib.rxg_flow_sums_host(_ptr(recs) if n else None, rec_kind, ptrs, None if lens is None else _ptr(lens), n, ntcb,
+                                flags, _ptr(buf) if cap else None, cap, _ptr(count))
+    if rc:
+        raise RxgError(f"rxg_flow_sums_host failed ({rc})")
+    return (buf if out is not None else buf[:min(int(count[0]), cap)].copy()), count
 
 
 # -------------------------------------------------------------------------- engine ---
@@ -989,6 +1038,29 @@ class Engine:
         rc = _lib.rxg_rx_opt_current(self.ctx, C.byref(p))
         _check(min(rc, 0), "rxg_rx_opt_current")
         return np.frombuffer(C.string_at(p.value, 16), dtype=RX_OPT_DTYPE)[0] if rc == 1 else None
+
+    def flow_sums_dev(self, recs: int, rec_kind: int, n: int, ntcb: int, out: int | None, cap: int, count: int,
+                      frames: int | None = None, lens: int | None = None, off64: int | None = None, slot0: int = 0,
+                      stride64: int = 0, flags: int = 0, stream=None):
+        """rxg_flow_sums_dev: one rxg_flow_sum (FLOW_SUM_DTYPE) at out + 40 * k for the k-th TCB, in
+        ascending tcb_idx, that the burst whose records are at `recs` dispatches a counted frame to;
+        count (3 u64, written) = {flows, DISPATCH records outside [0, ntcb), frames left out by
+        FS_TCP_OK_ONLY}.  All device addresses; frames / lens may be None for REC48."""
+        b = DevFlowSums(frames, off64, lens, slot0, stride64, n, rec_kind, recs, ntcb, flags, out, cap, count)
+        _check(_lib.rxg_flow_sums_dev(self.ctx, C.byref(b), stream), "rxg_flow_sums_dev")
+
+    def flow_sums_attach(self, sums_host: int, m: int):
+        """rxg_flow_sums_attach: a host copy (address) of a flow_sums_dev call's output for the next
+        rx replay; the caller keeps it alive until that replay returns."""
+        _check(_lib.rxg_flow_sums_attach(self.ctx, sums_host, m), "rxg_flow_sums_attach")
+
+    def flow_sum_current(self):
+        """Inside a replay's handler: (the FLOW_SUM_DTYPE summary of the replayed packet's flow (a
+        copy), the packet's index), or None (see rxg_flow_sum_current)."""
+        p, i = C.c_void_p(), C.c_uint32()
+        rc = _lib.rxg_flow_sum_current(self.ctx, C.byref(p), C.byref(i))
+        _check(min(rc, 0), "rxg_flow_sum_current")
+        return (np.frombuffer(C.string_at(p.value, 40), dtype=FLOW_SUM_DTYPE)[0], i.value) if rc == 1 else None
 
     def tx_build(self, payload: np.ndarray, flows: np.ndarray, segs: np.ndarray, off64=None, slot0: int = 0,
                  stride64: int = 0, opts=None):

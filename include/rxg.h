@@ -913,6 +913,109 @@ int rxg_rx_opts_attach(rxg_ctx *ctx, const rxg_rx_opt *opts_host, uint32_t n);
 int rxg_rx_opt_current(rxg_ctx *ctx, const rxg_rx_opt **out);
 
 /* ------------------------------------------------------------------------- */
+/* A burst summarised per flow from its records: what on_segment does per      */
+/* dispatched frame (tcp_in.c:66-71: the max_seq_received update and           */
+/* AdjustSendWindow(tcb, ack)) is a property of the flow, not of the packet.   */
+/* max_seq_received is the unsigned 32-bit maximum of sent_seq (tcp_in.c:66 is */
+/* a plain >, no serial-number arithmetic), and k calls AdjustSendWindow(tcb,  */
+/* a_1..a_k) leave the send window as one call with the unsigned maximum of    */
+/* the a_j does (tcp_windows.c:265 removes pairs with m_EndSeqNumber <=        */
+/* AckValue; the early returns at :236 and :241 return only where that loop    */
+/* would remove nothing).                                                      */
+/*                                                                             */
+/* Which frames count.  Frame i is counted when its record's verdict is        */
+/* RXG_V_DISPATCH, 0 <= tcb_idx < ntcb and, with RXG_FS_TCP_OK_ONLY, its       */
+/* record carries RXG_F_TCP_OK.  A DISPATCH record with tcb_idx outside        */
+/* [0, ntcb) is never followed: count[1] counts it.  A DISPATCH frame left out */
+/* by the checksum flag alone is counted in count[2].  Every other verdict is  */
+/* ignored.                                                                    */
+/*                                                                             */
+/* Where each field comes from.  datalen, tcp_flags, state and tcb_idx come    */
+/* from the record (rxg_rec8 decoded as rxg_rec8_expand does: state 7 becomes  */
+/* RXG_STATE_NONE).  seq and ack are, for RXG_REC8 and RXG_REC16, big-endian   */
+/* frame[38..42) and frame[42..46) with bytes at or beyond len[i] read as zero */
+/* (as the rx kernel and the reset build read truncated frames); for RXG_REC48 */
+/* they are the record's seq and ack and no frame byte is read: frames, off64  */
+/* and len may then be NULL.                                                   */
+/*                                                                             */
+/* Output.  One rxg_flow_sum per TCB with at least one counted frame, in       */
+/* ascending tcb_idx: out[k] is the k-th such TCB.  Entries with k >= cap are  */
+/* not written.  count is 3 words, WRITTEN (not added to): count[0] the number */
+/* of flows the burst touches whatever cap is (rxg_tx_reset_dev's cap / *count */
+/* rule), count[1] and count[2] as above.  The output is a pure function of    */
+/* the arguments: never of the grid, the stream, the mirror or an earlier call.*/
+/* ------------------------------------------------------------------------- */
+typedef struct rxg_flow_sum {   /* 40 bytes, arrays 8-byte aligned */
+    int32_t  tcb_idx;
+    uint32_t frames;        /* counted frames of this TCB                                    */
+    uint32_t max_seq;       /* unsigned max of ntohl(sent_seq)   (tcp_in.c:66-67)             */
+    uint32_t max_ack;       /* unsigned max of ntohl(recv_ack)   (one AdjustSendWindow call)  */
+    uint32_t first_idx;     /* lowest and highest packet index among them                    */
+    uint32_t last_idx;
+    uint32_t data_frames;   /* frames with datalen > 0                                       */
+    uint8_t  tcp_flags_or;  /* OR of their tcp_flags                                         */
+    uint8_t  state;         /* the state field of frame first_idx's record                   */
+    uint16_t reserved;      /* 0                                                             */
+    uint64_t data_bytes;    /* sum of datalen over frames with datalen > 0                   */
+} rxg_flow_sum;
+#define RXG_FS_TCP_OK_ONLY 0x1u  /* leave out frames without RXG_F_TCP_OK (RXG_OPS_VERIFY_TCP_CKSUM stacks) */
+#define RXG_FS_MAX_NTCB (1u << 24) /* rxg_rec8's index width */
+
+/* frames / off64 / len / slot0 / stride64 follow rxg_dev_rx_opts' rules and strided form (of a
+   counted frame only the 16 bytes at 32..47 are read, and only when len[i] > 38); recs are the
+   burst's n records as the burst wrote them.  Asynchronous on `stream`: four launches (the
+   accumulation, the per-tile counts of the touched bitmap, their scan, the expansion), no
+   workgroup waits on another; rxg_config.max_blocks caps the grids.  The context owns a dense
+   accumulator of ntcb entries and a touched bitmap that all calls share and every call leaves
+   all zero; they grow on demand.  One call at a time uses them: a call on another stream waits
+   (on the device, through an event) for the previous call on this context.
+   n == 0 writes count = {0, 0, 0} and nothing else.
+   -EINVAL: a NULL ctx, b, recs or count; out NULL with cap != 0; frames or len NULL unless
+   rec_kind is RXG_REC48; a bad rec_kind; ntcb 0 or over RXG_FS_MAX_NTCB; unknown flag bits;
+   frames not 16-, out or count not 8-, off64 not 4-, len not 2-byte aligned, recs not 8-
+   (RXG_REC8) or 16-byte aligned; where frames are read, stride64 0 or slot0 + (n - 1) *
+   stride64 over 2^32 - 1 in strided mode.  -ENOMEM: the accumulator cannot be allocated;
+   nothing is launched then.  A group's members are plain contexts for this call. */
+typedef struct rxg_dev_flow_sums {
+    const void *frames;       /* dev: the burst's frame pool; may be NULL for RXG_REC48          */
+    const uint32_t *off64;    /* dev, n entries; NULL = fixed stride (slot0 + i * stride64)      */
+    const uint16_t *len;      /* dev, n entries; may be NULL for RXG_REC48                       */
+    uint32_t slot0, stride64; /* used when off64 == NULL                                         */
+    uint32_t n;
+    uint32_t rec_kind;        /* RXG_REC8 / RXG_REC16 / RXG_REC48                                */
+    const void *recs;         /* dev: the burst's n records, as the burst wrote them             */
+    uint32_t ntcb;            /* 1 .. RXG_FS_MAX_NTCB: TCB indices at or past it are not followed */
+    uint32_t flags;           /* RXG_FS_*                                                        */
+    rxg_flow_sum *out;        /* dev, 8-byte aligned, cap entries                                */
+    uint64_t cap;
+    uint64_t *count;          /* dev, 3 words, WRITTEN: flows, DISPATCH out of range, left out   */
+} rxg_dev_flow_sums;
+int rxg_flow_sums_dev(rxg_ctx *ctx, const rxg_dev_flow_sums *b, void *stream);
+
+/* Host form of the rule (no context, no GPU), for host-buffer bursts (rxg_rx_burst): frame i
+   is frames[i][0 .. len[i]); frames and len may be NULL for RXG_REC48.  Returns 0; -EINVAL: recs
+   or count NULL (n != 0 for recs), out NULL with cap != 0, frames or len NULL unless RXG_REC48
+   (n != 0), a bad rec_kind, ntcb 0 or over RXG_FS_MAX_NTCB, unknown flag bits; -ENOMEM. */
+int rxg_flow_sums_host(const void *recs, uint32_t rec_kind, void *const *frames, const uint16_t *len,
+                       uint32_t n, uint32_t ntcb, uint32_t flags, rxg_flow_sum *out, uint64_t cap,
+                       uint64_t count[3]);
+
+/* Using the summaries during the replay.  rxg_flow_sums_attach names a host copy of a call's
+   `out` (m = min(count[0], cap) entries, ascending tcb_idx) for the burst the next
+   rxg_rx_replay call on this context replays; the attachment ends when that replay returns,
+   however it returns.  rxg_flow_sum_current is called from a handler (on_segment, tcpswitch)
+   while the replay runs a packet.  It returns 1, with *out the flow's summary and *pkt_idx the
+   packet's index, when the packet's record as the burst wrote it is a DISPATCH whose TCB is
+   in the attached list with first_idx <= index <= last_idx, and the replay did not replace
+   that record by re-classification.  It returns 0 otherwise: outside a replay, with nothing
+   attached, for a re-classified packet, or for a flow past cap.  (A frame a summary made with
+   RXG_FS_TCP_OK_ONLY left out reaches no handler under RXG_OPS_VERIFY_TCP_CKSUM.)
+   -EINVAL: ctx, out or pkt_idx NULL (attach: ctx NULL, a NULL array with m != 0, or entries
+   not strictly ascending in tcb_idx). */
+int rxg_flow_sums_attach(rxg_ctx *ctx, const rxg_flow_sum *sums_host, uint64_t m);
+int rxg_flow_sum_current(rxg_ctx *ctx, const rxg_flow_sum **out, uint32_t *pkt_idx);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
