@@ -1,7 +1,9 @@
 // rxg_ctx.h — the context behind the rxg C ABI (include/rxg.h), shared by the host-side
 // translation units (internal: not installed, not part of the ABI):
-//   rxg_host.cpp    context, TCB / ARP mirrors, launched bursts, tx, counters, and
+//   rxg_host.cpp    context, TCB / ARP mirrors, launched bursts, counters, and
 //                   HipTablePort, the device side of rxg_tablesync.h
+//   rxg_ops.cpp     the operations on a burst beside its classification: tx checksums, segment
+//                   build, reset build, transmit planner, received options, flow summary
 //   rxg_tablesync.h the device tables and the order of their writes against the kernels that
 //                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
@@ -16,6 +18,7 @@
 #include <climits>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <unordered_map>
 #include <vector>
 
@@ -79,16 +82,72 @@ struct HipTablePort {
     int table_upload(DevBuf &b, const void *src, size_t bytes);
 };
 
+// Scratch memory of the context that one call at a time uses (an operation's launches share it
+// and the next call overwrites it).  The rule, for calls on any streams: a call waits, on its
+// stream, for the previous call's last launch (the event, recorded at the end of every call,
+// even after a failed launch: whatever part of it was enqueued is waited for); before a buffer
+// is replaced by a larger one the host waits for that launch instead.
+struct SerialScratch {
+    const char *who;      // the entry point, for its error texts
+    DevBuf buf[3] = {};
+    hipEvent_t ev = nullptr;
+    bool open = false;    // begin() without its end()
+
+    // b (one of buf) grown to `bytes`, never shrunk.  zero: the new memory is zeroed on st.
+    // -ENOMEM when it cannot be had (b is then empty).
+    int grow(DevBuf &b, size_t bytes, bool zero, hipStream_t st)
+    {
+        if (b.p && b.bytes >= bytes) return 0;
+        if (ev) HIP_OK(hipEventSynchronize(ev));
+        if (b.p) HIP_OK(hipFree(b.p));
+        b.p = nullptr;
+        b.bytes = 0;
+        const size_t want = std::max<size_t>(bytes, 256);
+        if (hipMalloc(&b.p, want) != hipSuccess) {
+            (void)hipGetLastError();
+            b.p = nullptr;
+            return fail(-ENOMEM, "%s: %zu bytes of device memory", who, want);
+        }
+        b.bytes = want;
+        if (zero) HIP_OK(hipMemsetAsync(b.p, 0, want, st));
+        return 0;
+    }
+    // before the call's first launch on st
+    int begin(hipStream_t st)
+    {
+        if (ev) HIP_OK(hipStreamWaitEvent(st, ev, 0));
+        else HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        open = true;
+        return 0;
+    }
+    // after its last; returns the launches' error as the entry point's code (a call that
+    // never began, one of no frames, records nothing)
+    int end(hipStream_t st, hipError_t launch_error)
+    {
+        if (open) {
+            open = false;
+            HIP_OK(hipEventRecord(ev, st));
+        }
+        HIP_OK(launch_error);
+        return 0;
+    }
+    void destroy()
+    {
+        for (DevBuf &b : buf)
+            if (b.p) (void)hipFree(b.p);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// The operations whose launch grid the context works out once, at init (rxg_ctx::op_grid).
+enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridOps };
+
 struct rxg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t max_blocks = 0;        // rxg_config.max_blocks: grid cap (0 = occupancy grid)
-    uint32_t grid_pay = 512;        // rxg_rx_burst_payload_dev's grid (set at init)
-    uint32_t grid_txb = 0;          // rxg_tx_build_dev's occupancy grid (set at init)
-    uint32_t grid_txbo = 0;         // rxg_tx_build_opt_dev's
-    uint32_t grid_txr = 0;          // rxg_tx_reset_dev's (its build pass)
-    uint32_t grid_rxo = 0;          // rxg_rx_opts_dev's
-    uint32_t grid_txp = 0;          // rxg_tx_plan_dev's (its expand pass)
+    // grids by operation, set at init (rxg_init says what each is); 0: unknown (grid_cap)
+    uint32_t op_grid[kGridOps] = {512};
     // occupancy grids by [the by-reference hand-off's kernel][grid_slot(record kind)] (grid_for)
     uint32_t grid[2][4] = {};
     rxg::PackPool pack_pool;  // rxg_rx_burst's packing threads
@@ -164,13 +223,10 @@ struct rxg_ctx {
     hipEvent_t pm_ev = nullptr;
     int64_t replay_pos = -1;  // packet whose handlers rxg_rx_replay is running
 
-    // rxg_tx_reset_dev: the slice counts its three launches share, and the event that orders a
-    // call on another stream after the previous call's use of them (recorded after every call)
-    DevBuf d_rst_counts;
-    hipEvent_t rst_ev = nullptr;
-    // rxg_tx_plan_dev: the tile sums its launches share, under the same rule (txp_ev)
-    DevBuf d_txp_tiles;
-    hipEvent_t txp_ev = nullptr;
+    // rxg_tx_reset_dev: the slice counts its three launches share (buf[0])
+    SerialScratch rst{"rxg_tx_reset_dev"};
+    // rxg_tx_plan_dev: the tile sums its launches share (buf[0])
+    SerialScratch txp{"rxg_tx_plan_dev"};
     // rxg_reset_attach: host copies of a call's resets and their packet indices for the replay
     // that follows (cleared when it returns), and rxg_reset_take's cursor into them
     uint8_t *rst_host = nullptr;
@@ -181,12 +237,11 @@ struct rxg_ctx {
     const rxg_rx_opt *opt_host = nullptr;
     uint32_t opt_n = 0;
     bool opt_live = false;  // the running replay's burst has opt_n frames
-    // rxg_flow_sums_dev: the dense accumulator and the touched bitmap (all zero between calls),
-    // the tile counts, and the event that orders a call after the previous one (rst_ev's rule)
-    DevBuf d_fs_acc, d_fs_bits, d_fs_tiles;
-    hipEvent_t fs_ev = nullptr;
+    // rxg_flow_sums_dev: the dense accumulator and the touched bitmap (all zero between calls)
+    // and the tile counts (buf[kFsAcc .. kFsTiles])
+    enum { kFsAcc, kFsBits, kFsTiles };
+    SerialScratch fs{"rxg_flow_sums_dev"};
     bool fs_dirty = false;  // a launch failed part-way: both are zeroed again before the next
-    uint32_t grid_fs = 0;   // its accumulation's grid (set at init)
     // rxg_flow_sums_attach: a host copy of a call's summaries for the replay that follows
     // (cleared when it returns); rxg_flow_sum_current answers from it
     const rxg_flow_sum *fs_host = nullptr;
@@ -292,10 +347,14 @@ inline int grid_slot(uint32_t rec_kind)
 {
     return rec_kind == RXG_REC8 ? 1 : rec_kind == RXG_REC16 ? 2 : rec_kind == RXG_REC48 ? 3 : 0;
 }
+// (occupancy: a grid worked out at init, 0 where the device's properties could not be read)
+inline uint32_t grid_cap(const rxg_ctx *c, uint32_t occupancy)
+{
+    return c->max_blocks ? c->max_blocks : occupancy ? occupancy : 1024u;
+}
 inline uint32_t grid_for(const rxg_ctx *c, uint32_t rec_kind, bool by_ref = false)
 {
-    const uint32_t g = c->max_blocks ? c->max_blocks : c->grid[by_ref][grid_slot(rec_kind)];
-    return g ? g : 1024;
+    return grid_cap(c, c->grid[by_ref][grid_slot(rec_kind)]);
 }
 
 // rxg_host.cpp: the mirror upload, the replay bookkeeping of a burst set and its offsets.
@@ -315,5 +374,24 @@ inline unsigned long long *correction_row(rxg_ctx *c)
 }
 
 inline bool rec_kind_ok(uint32_t k) { return k == RXG_REC8 || k == RXG_REC16 || k == RXG_REC48; }
+
+// The alignment of a burst's records: the kernels read and write them with 8- or 16-byte
+// vector accesses.
+inline uintptr_t rec_align(uint32_t rec_kind) { return rec_kind == RXG_REC8 ? 8u : 16u; }
+
+// The strided mode of a frame source (off64 NULL: frame i at slot slot0 + i * stride64) must
+// name a stride and stay inside 2^32 slots.  burst >= 0: the text names that burst of a set.
+inline int check_frame_src(const char *who, const uint32_t *off64, uint32_t slot0, uint32_t stride64, uint32_t n,
+                           int burst = -1)
+{
+    if (off64) return 0;
+    if (!stride64) return fail(-EINVAL, "%s: stride64 0", who);
+    if (n && (uint64_t)slot0 + (uint64_t)(n - 1u) * stride64 > 0xFFFFFFFFull) {
+        char which[24] = "";
+        if (burst >= 0) snprintf(which, sizeof which, " burst %d:", burst);
+        return fail(-EINVAL, "%s:%s slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots", who, which);
+    }
+    return 0;
+}
 
 #pragma GCC visibility pop

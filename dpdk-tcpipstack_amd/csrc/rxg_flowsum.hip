@@ -28,15 +28,14 @@
 //
 // Roofline: HBM, algorithmic bytes = n * record size + 16 per counted frame (8- and 16-byte
 // records) + ntcb / 8 of bitmap + 40 per flow.
+#include "rxg_dev.h"
 #include "rxg_kernels.h"
 
 namespace rxg {
 namespace {
 
 struct FsArgs {
-    const uint8_t *frames;
-    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
-    const uint16_t *len;
+    FrameSrc src;                // (frames and len unused for RXG_REC48)
     const uint8_t *recs;
     FlowSumAcc *acc;
     uint32_t *bits;              // the bitmap (past the two left-out counters)
@@ -45,26 +44,8 @@ struct FsArgs {
     rxg_flow_sum *out;
     unsigned long long cap;
     unsigned long long *count;
-    uint32_t n, nslices, rec_kind, slot0, stride64, ntcb, flags, ntiles;
+    uint32_t n, nslices, rec_kind, ntcb, flags, ntiles;
 };
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint4 ld16(const uint8_t *p)
-{
-    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src_lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
-
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
-{
-    return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
-}
 
 // One flow's contribution: a frame's, or a wave's carried sum.
 struct Part {
@@ -145,26 +126,14 @@ __global__ __launch_bounds__(256) void flow_sum_acc(FsArgs a)
     for (uint32_t s = s0; s < s1; ++s) {
         const uint32_t i = s * 64u + lane;
         const bool in = i < a.n;
-        int32_t tcb = -1, dl = 0;
-        uint32_t verdict = 0xFFu, rfl = 0, tfl = 0;
+        RecFields f = {-1, 0xFFu, 0u, 0u, 0};  // past the burst's end: no verdict
         const uint8_t *r = a.recs + (size_t)i * a.rec_kind;
         if (in) {
-            if (a.rec_kind == RXG_REC8) {
-                const uint2 w = *reinterpret_cast<const uint2 *>(r);
-                tcb = (int32_t)(w.x & 0xFFFFFFu) - 1;
-                verdict = (w.x >> 24) & 7u;
-                tfl = w.y & 0xFFu;
-                rfl = (w.y >> 8) & 0x3Fu;
-                dl = (int32_t)((w.y >> 14) & 0x1FFFFu) - 128;
-            } else {
-                const uint4 w = *reinterpret_cast<const uint4 *>(r);
-                tcb = (int32_t)w.x;
-                verdict = w.z & 0xFFu;
-                tfl = (w.z >> 16) & 0xFFu;
-                rfl = w.z >> 24;
-                dl = (int32_t)w.w;
-            }
+            if (a.rec_kind == RXG_REC8) f = rec8_fields(*reinterpret_cast<const uint2 *>(r));
+            else f = rec16_fields(*reinterpret_cast<const uint4 *>(r));
         }
+        const int32_t tcb = f.tcb_idx, dl = f.datalen;
+        const uint32_t verdict = f.verdict, rfl = f.flags, tfl = f.tcp_flags;
         const bool disp = in && verdict == RXG_V_DISPATCH;
         const bool inr = disp && tcb >= 0 && (uint32_t)tcb < a.ntcb;
         const bool ok = !(a.flags & RXG_FS_TCP_OK_ONLY) || (rfl & RXG_F_TCP_OK);
@@ -180,10 +149,10 @@ __global__ __launch_bounds__(256) void flow_sum_acc(FsArgs a)
                 seq = w.x;
                 ack = w.y;
             } else {
-                const uint32_t off = a.off64 ? a.off64[i] : a.slot0 + i * a.stride64;
-                const int ln = (int)a.len[i];
+                const uint32_t off = frame_slot(a.src, i);
+                const int ln = (int)a.src.len[i];
                 if (ln > 38) {  // a byte of seq or ack lies inside the frame: its first line is readable
-                    const uint4 c = ld16(a.frames + (size_t)off * 64u + 32u);  // 64-bit: a pool may pass 4 GiB
+                    const uint4 c = ld16(a.src.frames + (size_t)off * 64u + 32u);  // 64-bit: a pool may pass 4 GiB
                     const uint32_t y = keep_bytes(c.y, ln - 36), z = keep_bytes(c.z, ln - 40),
                                    w = keep_bytes(c.w, ln - 44);
                     seq = __builtin_bswap32((y >> 16) | (z << 16));
@@ -261,36 +230,20 @@ __global__ __launch_bounds__(256) void flow_sum_count(FsArgs a)
     }
 }
 
-// tiles[0 .. ntiles) -> exclusive prefix sums in place (rxg_txreset.hip's scan, one entry per
+// tiles[0 .. ntiles) -> exclusive prefix sums in place (rxg_dev.h block_scan, one entry per
 // lane and round), count[0] = the total; the two left-out counters move to count[1..2] and
 // are zeroed for the next call.
 __global__ __launch_bounds__(1024) void flow_sum_scan(uint32_t *tiles, uint32_t ntiles, unsigned long long *left,
                                                       unsigned long long *count)
 {
     __shared__ uint32_t wsum[kFsScanLanes / 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     unsigned long long carry = 0;
     for (uint32_t base = 0; base < ntiles; base += kFsScanLanes) {
         const uint32_t e = base + threadIdx.x;
         const uint32_t t = e < ntiles ? tiles[e] : 0u;
-        uint32_t inc = t;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = lane_read(inc, (int)((lane - (uint32_t)d) & 63u));
-            if (lane >= (uint32_t)d) inc += up;
-        }
-        if (lane == 63u) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kFsScanLanes / 64u; ++w) {
-            const uint32_t x = wsum[w];
-            if (w < wave) before += x;
-            total += x;
-        }
-        __syncthreads();  // wsum is rewritten by the next round
-        if (e < ntiles) tiles[e] = (uint32_t)carry + before + inc - t;
-        carry += total;
+        const BlockScan<uint32_t> b = block_scan<uint32_t, kFsScanLanes>(t, wsum);
+        if (e < ntiles) tiles[e] = (uint32_t)carry + b.before + b.inc - t;
+        carry += b.total;
     }
     if (threadIdx.x == 0u) {
         count[0] = carry;
@@ -312,13 +265,7 @@ __global__ __launch_bounds__(256) void flow_sum_expand(FsArgs a)
         if (__ballot(w != 0u) == 0ull) continue;
         // set bits in the tile's words before this lane's
         const uint32_t pc = (uint32_t)__popc(w);
-        uint32_t inc = pc;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = lane_read(inc, (int)((lane - (uint32_t)d) & 63u));
-            if (lane >= (uint32_t)d) inc += up;
-        }
-        const uint32_t excl = inc - pc;
+        const uint32_t excl = wave_incl_scan(pc, lane) - pc;
         const unsigned long long base = a.tiles[t];
         for (uint32_t k = 0; k < kFsTileWords / 2u; ++k) {
             const int src = (int)(2u * k + (lane >> 5));
@@ -382,9 +329,7 @@ hipError_t launch_flow_sum(const LaunchFlowSum &F, hipStream_t st)
 {
     if (F.n == 0) return hipMemsetAsync(F.count, 0, 3 * sizeof(unsigned long long), st);
     FsArgs a;
-    a.frames = F.frames;
-    a.off64 = F.off64;
-    a.len = F.len;
+    a.src = F.src;
     a.recs = F.recs;
     a.acc = F.acc;
     a.left = reinterpret_cast<unsigned long long *>(F.bits);
@@ -396,8 +341,6 @@ hipError_t launch_flow_sum(const LaunchFlowSum &F, hipStream_t st)
     a.n = F.n;
     a.nslices = (uint32_t)(((uint64_t)F.n + 63u) / 64u);
     a.rec_kind = F.rec_kind;
-    a.slot0 = F.slot0;
-    a.stride64 = F.stride64;
     a.ntcb = F.ntcb;
     a.flags = F.flags;
     a.ntiles = fs_tiles(F.ntcb);

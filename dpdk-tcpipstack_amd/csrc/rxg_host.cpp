@@ -1,5 +1,5 @@
 // rxg_host.cpp — host side of the rxg C ABI (include/rxg.h): the context, mirrors, launched
-// bursts, tx and counters (the other entry points: rxg_server.cpp, rxg_replay.cpp,
+// bursts and counters (the other entry points: rxg_ops.cpp, rxg_server.cpp, rxg_replay.cpp,
 // rxg_util.cpp; the context itself: rxg_ctx.h).
 //
 // Owns one GPU context: its stream, the device TCB mirror (rebuilt from the host mirror
@@ -82,16 +82,18 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         // the fused burst + payload hand-off moves as many bytes out as in: 2 workgroups per CU
         // (8 waves) measured faster than the occupancy grid's 3 (C3 621 against 627 us, C4 174
         // against 177)
-        c->grid_pay = cus * 2u;
-        c->grid_txb = cus * (uint32_t)tx_build_blocks_per_cu(false);  // rxg_tx_build_dev's occupancy grid
-        c->grid_txbo = cus * (uint32_t)tx_build_blocks_per_cu(true);  // rxg_tx_build_opt_dev's
-        c->grid_txr = cus * (uint32_t)tx_reset_blocks_per_cu();  // rxg_tx_reset_dev's
-        c->grid_rxo = cus * (uint32_t)rx_opts_blocks_per_cu();  // rxg_rx_opts_dev's
-        c->grid_txp = cus * (uint32_t)tx_plan_blocks_per_cu();  // rxg_tx_plan_dev's
+        c->op_grid[kGridPay] = cus * 2u;
+        // the occupancy grids of the operations' kernels (rxg_ops.cpp; the reset's is its build
+        // pass's, the planner's its expand pass's)
+        c->op_grid[kGridTxBuild] = cus * (uint32_t)tx_build_blocks_per_cu(false);
+        c->op_grid[kGridTxBuildOpt] = cus * (uint32_t)tx_build_blocks_per_cu(true);
+        c->op_grid[kGridTxReset] = cus * (uint32_t)tx_reset_blocks_per_cu();
+        c->op_grid[kGridRxOpts] = cus * (uint32_t)rx_opts_blocks_per_cu();
+        c->op_grid[kGridTxPlan] = cus * (uint32_t)tx_plan_blocks_per_cu();
         // rxg_flow_sums_dev's accumulation: one workgroup per CU.  Every workgroup ends with one
         // set of atomics on its carried flow, and atomics on one line run one after the other:
         // 256 workgroups measured faster than 1 024 on every shape
-        c->grid_fs = cus;
+        c->op_grid[kGridFlowSum] = cus;
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -170,12 +172,9 @@ extern "C" int rxg_fini(rxg_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->tables.wait_readers(true);  // table readers still running on caller streams
     for (DevBuf *b : {&c->tables.buckets, &c->tables.listen, &c->d_sel, &c->d_fix, &c->tables.d_arp, &c->d_pg_status,
-                      &c->d_pg_ticket, &c->d_soff, &c->d_rst_counts, &c->d_txp_tiles, &c->d_fs_acc,
-                      &c->d_fs_bits, &c->d_fs_tiles})
+                      &c->d_pg_ticket, &c->d_soff})
         if (b->p) (void)hipFree(b->p);
-    if (c->rst_ev) (void)hipEventDestroy(c->rst_ev);
-    if (c->txp_ev) (void)hipEventDestroy(c->txp_ev);
-    if (c->fs_ev) (void)hipEventDestroy(c->fs_ev);
+    for (SerialScratch *s : {&c->rst, &c->txp, &c->fs}) s->destroy();
     if (c->h_pm) (void)hipHostFree(c->h_pm);
     if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
     c->tables.destroy();
@@ -502,17 +501,16 @@ int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, ui
     bool any = false;
     // the kernel reads descriptors as u32 / u16, frames in 16-byte chunks, and writes each
     // slice's records with 8- or 16-byte vector stores
-    const uintptr_t rec_align = rec_kind == RXG_REC8 ? 8u : 16u;
     for (uint32_t j = 0; j < k; ++j) {
         if (!bursts[j].n) continue;
         if ((!stride64 && !bursts[j].off64) || !bursts[j].len || !bursts[j].out)
             return fail(-EINVAL, "%s: NULL device pointer in burst %u", who, j);
-        if (stride64 && (uint64_t)bursts[j].pad + (uint64_t)(bursts[j].n - 1u) * stride64 > 0xFFFFFFFFull)
-            return fail(-EINVAL, "%s: burst %u: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots", who, j);
+        if (stride64)
+            if (int rc = check_frame_src(who, nullptr, bursts[j].pad, stride64, bursts[j].n, (int)j)) return rc;
         if (((uintptr_t)bursts[j].off64 & 3u) || ((uintptr_t)bursts[j].len & 1u) ||
-            ((uintptr_t)bursts[j].out & (rec_align - 1u)))
+            ((uintptr_t)bursts[j].out & (rec_align(rec_kind) - 1u)))
             return fail(-EINVAL, "%s: burst %u: off64 needs 4-byte, len 2-byte, out %u-byte alignment", who, j,
-                        (unsigned)rec_align);
+                        (unsigned)rec_align(rec_kind));
         any = true;
     }
     if (any && !frames) return fail(-EINVAL, "%s: NULL frame pool", who);
@@ -584,7 +582,7 @@ static int launch_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bu
         }
         L.counters = c->counters;
         // (the by-reference hand-off writes no payload: its kernel's occupancy grid)
-        L.max_blocks = pay && pay->arena && !c->max_blocks ? c->grid_pay : grid_for(c, rec_kind, pay != nullptr);
+        L.max_blocks = pay && pay->arena ? grid_cap(c, c->op_grid[kGridPay]) : grid_for(c, rec_kind, pay != nullptr);
         L.ipatch = c->tables.carried(&L.nipatch);  // (the first launch takes it)
         const hipError_t e = launch_rx(L, st);
         if (e != hipSuccess) {
@@ -684,320 +682,6 @@ int burst_offsets(rxg_ctx *c, hipStream_t st, const uint32_t **out)
         c->soff_stream = st;
     }
     *out = (const uint32_t *)c->d_soff.p;
-    return 0;
-}
-
-extern "C" int rxg_tx_cksum_dev(rxg_ctx *c, const rxg_dev_tx_batch *b, void *stream)
-{
-    if (!c || !b) return fail(-EINVAL, "rxg_tx_cksum_dev: NULL argument");
-    if (b->n && (!b->frames || !b->off64 || !b->len))
-        return fail(-EINVAL, "rxg_tx_cksum_dev: NULL device pointer");
-    if (b->n && (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u)))
-        return fail(-EINVAL, "rxg_tx_cksum_dev: frames need 16-byte, off64 4-byte, len 2-byte alignment");
-    int rc = set_device(c);
-    if (rc) return rc;
-    LaunchBurst one{b->off64, b->len, b->n, nullptr, 0u};
-    LaunchRx L;
-    std::memset(&L, 0, sizeof L);
-    L.frames = (const uint8_t *)b->frames;
-    L.bursts = &one;
-    L.nbursts = 1;
-    L.mode = 0;
-    L.counters = nullptr;
-    L.max_blocks = grid_for(c, 0);
-    HIP_OK(launch_rx(L, pick(c, stream)));
-    return 0;
-}
-
-static_assert(sizeof(rxg_tx_flow) == 32 && sizeof(rxg_tx_seg) == 32 && sizeof(rxg_dev_tx_build) == 80,
-              "transmit segment build layouts");
-
-// rxg_tx_build_dev and rxg_tx_build_opt_dev (`opt`: its block table): one argument check, one launch
-static int tx_build_call(const char *who, rxg_ctx *c, const rxg_dev_tx_build *b, const rxg_dev_tx_build_opt *opt,
-                         void *stream)
-{
-    if (!c || !b) return fail(-EINVAL, "%s: NULL argument", who);
-    if (b->n == 0) return 0;
-    if (!b->payload || !b->flows || !b->segs || !b->frames || !b->len)
-        return fail(-EINVAL, "%s: NULL device pointer", who);
-    if (((uintptr_t)b->payload & 15u) || ((uintptr_t)b->frames & 63u) || ((uintptr_t)b->segs & 7u) ||
-        ((uintptr_t)b->flows & 7u) || ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) ||
-        ((uintptr_t)b->stats & 7u))
-        return fail(-EINVAL, "%s: payload needs 16-byte, frames 64-byte, segs, flows and stats "
-                             "8-byte, off64 4-byte, len 2-byte alignment", who);
-    if (!b->off64) {
-        if (!b->stride64) return fail(-EINVAL, "%s: stride64 0", who);
-        if ((uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
-            return fail(-EINVAL, "%s: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots", who);
-    }
-    if (opt) {
-        if ((uintptr_t)opt->opts & 15u) return fail(-EINVAL, "%s: opts needs 16-byte alignment", who);
-        if (!opt->opts && opt->nopts) return fail(-EINVAL, "%s: NULL opts with nopts %u", who, opt->nopts);
-    }
-    int rc = set_device(c);
-    if (rc) return rc;
-    LaunchTxBuild L;
-    L.payload = (const uint8_t *)b->payload;
-    L.payload_bytes = b->payload_bytes;
-    L.flows = b->flows;
-    L.nflows = b->nflows;
-    L.n = b->n;
-    L.segs = b->segs;
-    L.frames = (uint8_t *)b->frames;
-    L.off64 = b->off64;
-    L.slot0 = b->slot0;
-    L.stride64 = b->stride64;
-    L.len = b->len;
-    L.stats = (unsigned long long *)b->stats;
-    const uint32_t grid = opt ? c->grid_txbo : c->grid_txb;
-    L.max_blocks = c->max_blocks ? c->max_blocks : (grid ? grid : 1024u);  // (as grid_for)
-    L.with_opts = opt != nullptr;
-    L.opts = opt ? opt->opts : nullptr;
-    L.nopts = opt ? opt->nopts : 0u;
-    HIP_OK(launch_tx_build(L, pick(c, stream)));
-    return 0;
-}
-
-extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *stream)
-{
-    return tx_build_call("rxg_tx_build_dev", c, b, nullptr, stream);
-}
-
-static_assert(sizeof(rxg_tx_opt) == 48 && sizeof(rxg_dev_tx_build_opt) == 96, "option build layouts");
-
-extern "C" int rxg_tx_build_opt_dev(rxg_ctx *c, const rxg_dev_tx_build_opt *b, void *stream)
-{
-    return tx_build_call("rxg_tx_build_opt_dev", c, b ? &b->b : nullptr, b, stream);
-}
-
-static_assert(sizeof(rxg_dev_tx_reset) == 88, "reset build layout");
-
-extern "C" int rxg_tx_reset_dev(rxg_ctx *c, const rxg_dev_tx_reset *b, void *stream)
-{
-    if (!c || !b) return fail(-EINVAL, "rxg_tx_reset_dev: NULL argument");
-    if (!b->frames || !b->len || !b->recs || !b->out || !b->idx || !b->count)
-        return fail(-EINVAL, "rxg_tx_reset_dev: NULL device pointer");
-    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_tx_reset_dev: rec_kind %u", b->rec_kind);
-    const uintptr_t rec_align = b->rec_kind == RXG_REC8 ? 8u : 16u;  // (as rxg_rx_burst_dev)
-    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 63u) || ((uintptr_t)b->idx & 3u) ||
-        ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->count & 7u) ||
-        ((uintptr_t)b->recs & (rec_align - 1u)))
-        return fail(-EINVAL, "rxg_tx_reset_dev: frames need 16-byte, out 64-byte, idx and off64 4-byte, len 2-byte, "
-                             "count 8-byte, recs %u-byte alignment", (unsigned)rec_align);
-    if (!b->off64) {
-        if (!b->stride64) return fail(-EINVAL, "rxg_tx_reset_dev: stride64 0");
-        if (b->n && (uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
-            return fail(-EINVAL, "rxg_tx_reset_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
-    }
-    int rc = set_device(c);
-    if (rc) return rc;
-    hipStream_t st = pick(c, stream);
-    LaunchTxReset L;
-    L.frames = (const uint8_t *)b->frames;
-    L.off64 = b->off64;
-    L.len = b->len;
-    L.slot0 = b->slot0;
-    L.stride64 = b->stride64;
-    L.n = b->n;
-    L.rec_kind = b->rec_kind;
-    L.recs = (const uint8_t *)b->recs;
-    L.out = (uint8_t *)b->out;
-    L.idx = b->idx;
-    L.cap = b->cap;
-    L.count = (unsigned long long *)b->count;
-    L.counts = nullptr;
-    L.ip_id0 = b->ip_id0;
-    std::memcpy(L.src_mac, b->src_mac, 6);
-    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txr ? c->grid_txr : 1024u);  // (as grid_for)
-    if (b->n) {
-        // One call at a time uses the context's slice counts: a call waits, on its stream, for
-        // the previous call's last launch (rst_ev); before the buffer is replaced for a larger
-        // n the host waits for that launch instead.
-        const size_t need = tx_reset_count_bytes(b->n);
-        if (c->rst_ev && c->d_rst_counts.bytes < need) HIP_OK(hipEventSynchronize(c->rst_ev));
-        if ((rc = ensure(c->d_rst_counts, need))) return rc;
-        if (c->rst_ev) HIP_OK(hipStreamWaitEvent(st, c->rst_ev, 0));
-        else HIP_OK(hipEventCreateWithFlags(&c->rst_ev, hipEventDisableTiming));
-        L.counts = (uint32_t *)c->d_rst_counts.p;
-    }
-    const hipError_t e = launch_tx_reset(L, st);
-    // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
-    if (b->n) HIP_OK(hipEventRecord(c->rst_ev, st));
-    HIP_OK(e);
-    return 0;
-}
-
-static_assert(sizeof(rxg_tx_send) == 40 && sizeof(rxg_dev_tx_plan) == 80, "device planner layouts");
-
-extern "C" int rxg_tx_plan_dev(rxg_ctx *c, const rxg_dev_tx_plan *b, void *stream)
-{
-    if (!c || !b) return fail(-EINVAL, "rxg_tx_plan_dev: NULL argument");
-    if (!b->sends || !b->first || !b->count || (!b->segs && b->cap))
-        return fail(-EINVAL, "rxg_tx_plan_dev: NULL device pointer");
-    if (((uintptr_t)b->sends & 7u) || ((uintptr_t)b->segs & 7u) || ((uintptr_t)b->first & 7u) ||
-        ((uintptr_t)b->count & 7u) || ((uintptr_t)b->opts & 15u) || ((uintptr_t)b->next_seq & 3u) ||
-        ((uintptr_t)b->send_opt & 3u))
-        return fail(-EINVAL, "rxg_tx_plan_dev: sends, segs, first and count need 8-byte, opts 16-byte, next_seq and "
-                             "send_opt 4-byte alignment");
-    if (b->mss == 0 || b->mss > RXG_TX_MAX_DATA) return fail(-EINVAL, "rxg_tx_plan_dev: mss %u", b->mss);
-    if (!b->opts && b->nopts) return fail(-EINVAL, "rxg_tx_plan_dev: NULL opts with nopts %u", b->nopts);
-    int rc = set_device(c);
-    if (rc) return rc;
-    hipStream_t st = pick(c, stream);
-    LaunchTxPlan L;
-    L.sends = b->sends;
-    L.nsends = b->nsends;
-    L.mss = b->mss;
-    L.send_opt = b->send_opt;
-    L.opts = b->opts;
-    L.nopts = b->nopts;
-    L.segs = b->segs;
-    L.cap = b->cap;
-    L.first = (unsigned long long *)b->first;
-    L.next_seq = b->next_seq;
-    L.count = (unsigned long long *)b->count;
-    L.tiles = nullptr;
-    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_txp ? c->grid_txp : 1024u);  // (as grid_for)
-    if (b->nsends) {
-        // One call at a time uses the context's tile sums (rxg_tx_reset_dev's rule): a call
-        // waits, on its stream, for the previous call's last launch (txp_ev); before the buffer
-        // is replaced for more sends the host waits for that launch instead.
-        const size_t need = tx_plan_tile_bytes(b->nsends);
-        if (c->txp_ev && c->d_txp_tiles.bytes < need) HIP_OK(hipEventSynchronize(c->txp_ev));
-        if ((rc = ensure(c->d_txp_tiles, need))) return rc;
-        if (c->txp_ev) HIP_OK(hipStreamWaitEvent(st, c->txp_ev, 0));
-        else HIP_OK(hipEventCreateWithFlags(&c->txp_ev, hipEventDisableTiming));
-        L.tiles = c->d_txp_tiles.p;
-    }
-    const hipError_t e = launch_tx_plan(L, st);
-    // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
-    if (b->nsends) HIP_OK(hipEventRecord(c->txp_ev, st));
-    HIP_OK(e);
-    return 0;
-}
-
-static_assert(sizeof(rxg_rx_opt) == 16 && sizeof(rxg_dev_rx_opts) == 56, "received-option layouts");
-
-extern "C" int rxg_rx_opts_dev(rxg_ctx *c, const rxg_dev_rx_opts *b, void *stream)
-{
-    if (!c || !b) return fail(-EINVAL, "rxg_rx_opts_dev: NULL argument");
-    if (!b->frames || !b->len || !b->recs || !b->out) return fail(-EINVAL, "rxg_rx_opts_dev: NULL device pointer");
-    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_rx_opts_dev: rec_kind %u", b->rec_kind);
-    const uintptr_t rec_align = b->rec_kind == RXG_REC8 ? 8u : 16u;  // (as rxg_rx_burst_dev)
-    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 15u) || ((uintptr_t)b->off64 & 3u) ||
-        ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align - 1u)))
-        return fail(-EINVAL, "rxg_rx_opts_dev: frames and out need 16-byte, off64 4-byte, len 2-byte, recs %u-byte "
-                             "alignment", (unsigned)rec_align);
-    if (!b->off64) {
-        if (!b->stride64) return fail(-EINVAL, "rxg_rx_opts_dev: stride64 0");
-        if (b->n && (uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
-            return fail(-EINVAL, "rxg_rx_opts_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
-    }
-    if (!b->n) return 0;
-    int rc = set_device(c);
-    if (rc) return rc;
-    LaunchRxOpts L;
-    L.frames = (const uint8_t *)b->frames;
-    L.off64 = b->off64;
-    L.len = b->len;
-    L.slot0 = b->slot0;
-    L.stride64 = b->stride64;
-    L.n = b->n;
-    L.rec_kind = b->rec_kind;
-    L.recs = (const uint8_t *)b->recs;
-    L.out = (uint8_t *)b->out;
-    L.max_blocks = c->max_blocks ? c->max_blocks : (c->grid_rxo ? c->grid_rxo : 1024u);  // (as grid_for)
-    HIP_OK(launch_rx_opts(L, pick(c, stream)));
-    return 0;
-}
-
-static_assert(sizeof(rxg_flow_sum) == 40 && sizeof(rxg_dev_flow_sums) == 80, "flow summary layouts");
-
-// b grown to `bytes` (never shrunk) for rxg_flow_sums_dev.  zero: the new memory is zeroed on
-// st -- the old held nothing but zeroes once the previous call was done, which the host waits
-// for before the buffer is replaced.  -ENOMEM when it cannot be had (b is then empty).
-static int fs_grow(rxg_ctx *c, DevBuf &b, size_t bytes, bool zero, hipStream_t st)
-{
-    if (b.p && b.bytes >= bytes) return 0;
-    if (c->fs_ev) HIP_OK(hipEventSynchronize(c->fs_ev));
-    if (b.p) HIP_OK(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    const size_t want = std::max<size_t>(bytes, 256);
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        return fail(-ENOMEM, "rxg_flow_sums_dev: %zu bytes of device memory", want);
-    }
-    b.bytes = want;
-    if (zero) HIP_OK(hipMemsetAsync(b.p, 0, want, st));
-    return 0;
-}
-
-extern "C" int rxg_flow_sums_dev(rxg_ctx *c, const rxg_dev_flow_sums *b, void *stream)
-{
-    if (!c || !b) return fail(-EINVAL, "rxg_flow_sums_dev: NULL argument");
-    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_flow_sums_dev: rec_kind %u", b->rec_kind);
-    const bool reads_frames = b->rec_kind != RXG_REC48;
-    if (!b->recs || !b->count || (!b->out && b->cap) || (reads_frames && (!b->frames || !b->len)))
-        return fail(-EINVAL, "rxg_flow_sums_dev: NULL device pointer");
-    if (b->ntcb == 0 || b->ntcb > RXG_FS_MAX_NTCB) return fail(-EINVAL, "rxg_flow_sums_dev: ntcb %u", b->ntcb);
-    if (b->flags & ~RXG_FS_TCP_OK_ONLY) return fail(-EINVAL, "rxg_flow_sums_dev: unknown flags 0x%x", b->flags);
-    const uintptr_t rec_align = b->rec_kind == RXG_REC8 ? 8u : 16u;  // (as rxg_rx_burst_dev)
-    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 7u) || ((uintptr_t)b->count & 7u) ||
-        ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align - 1u)))
-        return fail(-EINVAL, "rxg_flow_sums_dev: frames need 16-byte, out and count 8-byte, off64 4-byte, len 2-byte, "
-                             "recs %u-byte alignment", (unsigned)rec_align);
-    if (reads_frames && !b->off64) {
-        if (!b->stride64) return fail(-EINVAL, "rxg_flow_sums_dev: stride64 0");
-        if (b->n && (uint64_t)b->slot0 + (uint64_t)(b->n - 1u) * b->stride64 > 0xFFFFFFFFull)
-            return fail(-EINVAL, "rxg_flow_sums_dev: slot0 + (n - 1) * stride64 exceeds 2^32 - 1 slots");
-    }
-    int rc = set_device(c);
-    if (rc) return rc;
-    hipStream_t st = pick(c, stream);
-    LaunchFlowSum L;
-    L.frames = reads_frames ? (const uint8_t *)b->frames : nullptr;
-    L.off64 = b->off64;
-    L.len = b->len;
-    L.slot0 = b->slot0;
-    L.stride64 = b->stride64;
-    L.n = b->n;
-    L.rec_kind = b->rec_kind;
-    L.recs = (const uint8_t *)b->recs;
-    L.ntcb = b->ntcb;
-    L.flags = b->flags;
-    L.out = b->out;
-    L.cap = b->cap;
-    L.count = (unsigned long long *)b->count;
-    L.acc = nullptr;
-    L.bits = nullptr;
-    L.tiles = nullptr;
-    L.max_blocks = c->max_blocks;
-    L.acc_blocks = c->grid_fs ? c->grid_fs : 1024u;
-    if (b->n) {
-        // One call at a time uses the context's accumulator, bitmap and tile counts
-        // (rxg_tx_reset_dev's rule): a call waits, on its stream, for the previous call's last
-        // launch (fs_ev); before a buffer is replaced for a larger ntcb the host waits instead.
-        if ((rc = fs_grow(c, c->d_fs_acc, flow_sum_bytes(b->ntcb), true, st))) return rc;
-        if ((rc = fs_grow(c, c->d_fs_bits, flow_sum_bits_bytes(b->ntcb), true, st))) return rc;
-        if ((rc = fs_grow(c, c->d_fs_tiles, flow_sum_tile_bytes(b->ntcb), false, st))) return rc;
-        if (c->fs_ev) HIP_OK(hipStreamWaitEvent(st, c->fs_ev, 0));
-        else HIP_OK(hipEventCreateWithFlags(&c->fs_ev, hipEventDisableTiming));
-        if (c->fs_dirty) {
-            HIP_OK(hipMemsetAsync(c->d_fs_acc.p, 0, c->d_fs_acc.bytes, st));
-            HIP_OK(hipMemsetAsync(c->d_fs_bits.p, 0, c->d_fs_bits.bytes, st));
-            c->fs_dirty = false;
-        }
-        L.acc = (FlowSumAcc *)c->d_fs_acc.p;
-        L.bits = (uint32_t *)c->d_fs_bits.p;
-        L.tiles = (uint32_t *)c->d_fs_tiles.p;
-    }
-    const hipError_t e = launch_flow_sum(L, st);
-    if (b->n && e != hipSuccess) c->fs_dirty = true;
-    // (recorded even after a failed launch: whatever part of it was enqueued is waited for)
-    if (b->n) HIP_OK(hipEventRecord(c->fs_ev, st));
-    HIP_OK(e);
     return 0;
 }
 

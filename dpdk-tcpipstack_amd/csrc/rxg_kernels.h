@@ -68,6 +68,16 @@ struct LaunchPayload {
 
 hipError_t launch_rx(const LaunchRx &L, hipStream_t st);
 
+// Where an operation on a burst finds its frames: frame i is at frames + 64 * off64[i], or with
+// off64 null (strided mode) at slot slot0 + i * stride64; len[i] is its length.  A member of
+// the launch structs below and of their kernels' arguments (rxg_dev.h frame_slot).
+struct FrameSrc {
+    const uint8_t *frames;
+    const uint32_t *off64;
+    const uint16_t *len;
+    uint32_t slot0, stride64;
+};
+
 // Latency mode (rxg_server_*): a persistent set of workgroups that classifies one burst after
 // another.  The host posts a request in a mailbox of fine-grained (coherent) host memory and
 // spins on its `done`; workgroup 0 polls the mailbox and hands each request to the others
@@ -181,10 +191,7 @@ int tx_build_blocks_per_cu(bool with_opts);  // resident 256-thread workgroups p
 // rxg_txreset.hip: reset replies from a burst's records (rxg_tx_reset_dev): a count pass, a
 // one-workgroup scan and a build pass on `st` (n == 0: *count = 0 only)
 struct LaunchTxReset {
-    const uint8_t *frames;
-    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
-    const uint16_t *len;
-    uint32_t slot0, stride64;
+    FrameSrc src;
     uint32_t n;
     uint32_t rec_kind;
     const uint8_t *recs;
@@ -223,10 +230,7 @@ int tx_plan_blocks_per_cu();  // resident 256-thread workgroups per CU of the ex
 // rxg_rxopt.hip: the TCP options of a burst's segments (rxg_rx_opts_dev), one launch on `st`
 // (n == 0: none)
 struct LaunchRxOpts {
-    const uint8_t *frames;
-    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
-    const uint16_t *len;
-    uint32_t slot0, stride64;
+    FrameSrc src;
     uint32_t n;
     uint32_t rec_kind;
     const uint8_t *recs;
@@ -250,10 +254,7 @@ constexpr uint32_t kFsTileWords = 64;                  // bitmap words per count
 constexpr uint32_t kFsTileTcbs = kFsTileWords * 32u;   // TCBs per count tile
 constexpr uint32_t kFsScanLanes = 1024;                // tiles per round of the scan
 struct LaunchFlowSum {
-    const uint8_t *frames;  // may be nullptr for RXG_REC48
-    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
-    const uint16_t *len;
-    uint32_t slot0, stride64;
+    FrameSrc src;           // frames may be nullptr for RXG_REC48
     uint32_t n;
     uint32_t rec_kind;
     const uint8_t *recs;

@@ -1,0 +1,249 @@
+// rxg_ops.cpp — the operations on a burst beside its classification (include/rxg.h): tx
+// checksums, segment build with and without options, reset build, transmit planner,
+// received-option parse, flow summary.  Each entry point checks its arguments, fills its
+// kernels' launch struct (rxg_kernels.h) and launches on the caller's stream; what they share
+// -- rec_align, check_frame_src, grid_cap, SerialScratch -- is in rxg_ctx.h.
+#include <cstring>
+
+#include "rxg_ctx.h"
+
+using namespace rxg;
+
+extern "C" int rxg_tx_cksum_dev(rxg_ctx *c, const rxg_dev_tx_batch *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_tx_cksum_dev: NULL argument");
+    if (b->n && (!b->frames || !b->off64 || !b->len))
+        return fail(-EINVAL, "rxg_tx_cksum_dev: NULL device pointer");
+    if (b->n && (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u)))
+        return fail(-EINVAL, "rxg_tx_cksum_dev: frames need 16-byte, off64 4-byte, len 2-byte alignment");
+    int rc = set_device(c);
+    if (rc) return rc;
+    LaunchBurst one{b->off64, b->len, b->n, nullptr, 0u};
+    LaunchRx L;
+    std::memset(&L, 0, sizeof L);
+    L.frames = (const uint8_t *)b->frames;
+    L.bursts = &one;
+    L.nbursts = 1;
+    L.mode = 0;
+    L.counters = nullptr;
+    L.max_blocks = grid_for(c, 0);
+    HIP_OK(launch_rx(L, pick(c, stream)));
+    return 0;
+}
+
+static_assert(sizeof(rxg_tx_flow) == 32 && sizeof(rxg_tx_seg) == 32 && sizeof(rxg_dev_tx_build) == 80,
+              "transmit segment build layouts");
+
+// rxg_tx_build_dev and rxg_tx_build_opt_dev (`opt`: its block table): one argument check, one launch
+static int tx_build_call(const char *who, rxg_ctx *c, const rxg_dev_tx_build *b, const rxg_dev_tx_build_opt *opt,
+                         void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "%s: NULL argument", who);
+    if (b->n == 0) return 0;
+    if (!b->payload || !b->flows || !b->segs || !b->frames || !b->len)
+        return fail(-EINVAL, "%s: NULL device pointer", who);
+    if (((uintptr_t)b->payload & 15u) || ((uintptr_t)b->frames & 63u) || ((uintptr_t)b->segs & 7u) ||
+        ((uintptr_t)b->flows & 7u) || ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) ||
+        ((uintptr_t)b->stats & 7u))
+        return fail(-EINVAL, "%s: payload needs 16-byte, frames 64-byte, segs, flows and stats "
+                             "8-byte, off64 4-byte, len 2-byte alignment", who);
+    int rc = check_frame_src(who, b->off64, b->slot0, b->stride64, b->n);
+    if (rc) return rc;
+    if (opt) {
+        if ((uintptr_t)opt->opts & 15u) return fail(-EINVAL, "%s: opts needs 16-byte alignment", who);
+        if (!opt->opts && opt->nopts) return fail(-EINVAL, "%s: NULL opts with nopts %u", who, opt->nopts);
+    }
+    if ((rc = set_device(c))) return rc;
+    LaunchTxBuild L;
+    L.payload = (const uint8_t *)b->payload;
+    L.payload_bytes = b->payload_bytes;
+    L.flows = b->flows;
+    L.nflows = b->nflows;
+    L.n = b->n;
+    L.segs = b->segs;
+    L.frames = (uint8_t *)b->frames;
+    L.off64 = b->off64;
+    L.slot0 = b->slot0;
+    L.stride64 = b->stride64;
+    L.len = b->len;
+    L.stats = (unsigned long long *)b->stats;
+    L.max_blocks = grid_cap(c, c->op_grid[opt ? kGridTxBuildOpt : kGridTxBuild]);
+    L.with_opts = opt != nullptr;
+    L.opts = opt ? opt->opts : nullptr;
+    L.nopts = opt ? opt->nopts : 0u;
+    HIP_OK(launch_tx_build(L, pick(c, stream)));
+    return 0;
+}
+
+extern "C" int rxg_tx_build_dev(rxg_ctx *c, const rxg_dev_tx_build *b, void *stream)
+{
+    return tx_build_call("rxg_tx_build_dev", c, b, nullptr, stream);
+}
+
+static_assert(sizeof(rxg_tx_opt) == 48 && sizeof(rxg_dev_tx_build_opt) == 96, "option build layouts");
+
+extern "C" int rxg_tx_build_opt_dev(rxg_ctx *c, const rxg_dev_tx_build_opt *b, void *stream)
+{
+    return tx_build_call("rxg_tx_build_opt_dev", c, b ? &b->b : nullptr, b, stream);
+}
+
+static_assert(sizeof(rxg_dev_tx_reset) == 88, "reset build layout");
+
+extern "C" int rxg_tx_reset_dev(rxg_ctx *c, const rxg_dev_tx_reset *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_tx_reset_dev: NULL argument");
+    if (!b->frames || !b->len || !b->recs || !b->out || !b->idx || !b->count)
+        return fail(-EINVAL, "rxg_tx_reset_dev: NULL device pointer");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_tx_reset_dev: rec_kind %u", b->rec_kind);
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 63u) || ((uintptr_t)b->idx & 3u) ||
+        ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->count & 7u) ||
+        ((uintptr_t)b->recs & (rec_align(b->rec_kind) - 1u)))
+        return fail(-EINVAL, "rxg_tx_reset_dev: frames need 16-byte, out 64-byte, idx and off64 4-byte, len 2-byte, "
+                             "count 8-byte, recs %u-byte alignment", (unsigned)rec_align(b->rec_kind));
+    int rc = check_frame_src("rxg_tx_reset_dev", b->off64, b->slot0, b->stride64, b->n);
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchTxReset L;
+    L.src = FrameSrc{(const uint8_t *)b->frames, b->off64, b->len, b->slot0, b->stride64};
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.out = (uint8_t *)b->out;
+    L.idx = b->idx;
+    L.cap = b->cap;
+    L.count = (unsigned long long *)b->count;
+    L.counts = nullptr;
+    L.ip_id0 = b->ip_id0;
+    std::memcpy(L.src_mac, b->src_mac, 6);
+    L.max_blocks = grid_cap(c, c->op_grid[kGridTxReset]);
+    if (b->n) {
+        DevBuf &counts = c->rst.buf[0];
+        if ((rc = c->rst.grow(counts, tx_reset_count_bytes(b->n), false, st))) return rc;
+        if ((rc = c->rst.begin(st))) return rc;
+        L.counts = (uint32_t *)counts.p;
+    }
+    return c->rst.end(st, launch_tx_reset(L, st));
+}
+
+static_assert(sizeof(rxg_tx_send) == 40 && sizeof(rxg_dev_tx_plan) == 80, "device planner layouts");
+
+extern "C" int rxg_tx_plan_dev(rxg_ctx *c, const rxg_dev_tx_plan *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_tx_plan_dev: NULL argument");
+    if (!b->sends || !b->first || !b->count || (!b->segs && b->cap))
+        return fail(-EINVAL, "rxg_tx_plan_dev: NULL device pointer");
+    if (((uintptr_t)b->sends & 7u) || ((uintptr_t)b->segs & 7u) || ((uintptr_t)b->first & 7u) ||
+        ((uintptr_t)b->count & 7u) || ((uintptr_t)b->opts & 15u) || ((uintptr_t)b->next_seq & 3u) ||
+        ((uintptr_t)b->send_opt & 3u))
+        return fail(-EINVAL, "rxg_tx_plan_dev: sends, segs, first and count need 8-byte, opts 16-byte, next_seq and "
+                             "send_opt 4-byte alignment");
+    if (b->mss == 0 || b->mss > RXG_TX_MAX_DATA) return fail(-EINVAL, "rxg_tx_plan_dev: mss %u", b->mss);
+    if (!b->opts && b->nopts) return fail(-EINVAL, "rxg_tx_plan_dev: NULL opts with nopts %u", b->nopts);
+    int rc = set_device(c);
+    if (rc) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchTxPlan L;
+    L.sends = b->sends;
+    L.nsends = b->nsends;
+    L.mss = b->mss;
+    L.send_opt = b->send_opt;
+    L.opts = b->opts;
+    L.nopts = b->nopts;
+    L.segs = b->segs;
+    L.cap = b->cap;
+    L.first = (unsigned long long *)b->first;
+    L.next_seq = b->next_seq;
+    L.count = (unsigned long long *)b->count;
+    L.tiles = nullptr;
+    L.max_blocks = grid_cap(c, c->op_grid[kGridTxPlan]);
+    if (b->nsends) {
+        DevBuf &tiles = c->txp.buf[0];
+        if ((rc = c->txp.grow(tiles, tx_plan_tile_bytes(b->nsends), false, st))) return rc;
+        if ((rc = c->txp.begin(st))) return rc;
+        L.tiles = tiles.p;
+    }
+    return c->txp.end(st, launch_tx_plan(L, st));
+}
+
+static_assert(sizeof(rxg_rx_opt) == 16 && sizeof(rxg_dev_rx_opts) == 56, "received-option layouts");
+
+extern "C" int rxg_rx_opts_dev(rxg_ctx *c, const rxg_dev_rx_opts *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_rx_opts_dev: NULL argument");
+    if (!b->frames || !b->len || !b->recs || !b->out) return fail(-EINVAL, "rxg_rx_opts_dev: NULL device pointer");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_rx_opts_dev: rec_kind %u", b->rec_kind);
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 15u) || ((uintptr_t)b->off64 & 3u) ||
+        ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align(b->rec_kind) - 1u)))
+        return fail(-EINVAL, "rxg_rx_opts_dev: frames and out need 16-byte, off64 4-byte, len 2-byte, recs %u-byte "
+                             "alignment", (unsigned)rec_align(b->rec_kind));
+    int rc = check_frame_src("rxg_rx_opts_dev", b->off64, b->slot0, b->stride64, b->n);
+    if (rc) return rc;
+    if (!b->n) return 0;
+    if ((rc = set_device(c))) return rc;
+    LaunchRxOpts L;
+    L.src = FrameSrc{(const uint8_t *)b->frames, b->off64, b->len, b->slot0, b->stride64};
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.out = (uint8_t *)b->out;
+    L.max_blocks = grid_cap(c, c->op_grid[kGridRxOpts]);
+    HIP_OK(launch_rx_opts(L, pick(c, stream)));
+    return 0;
+}
+
+static_assert(sizeof(rxg_flow_sum) == 40 && sizeof(rxg_dev_flow_sums) == 80, "flow summary layouts");
+
+extern "C" int rxg_flow_sums_dev(rxg_ctx *c, const rxg_dev_flow_sums *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_flow_sums_dev: NULL argument");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_flow_sums_dev: rec_kind %u", b->rec_kind);
+    const bool reads_frames = b->rec_kind != RXG_REC48;
+    if (!b->recs || !b->count || (!b->out && b->cap) || (reads_frames && (!b->frames || !b->len)))
+        return fail(-EINVAL, "rxg_flow_sums_dev: NULL device pointer");
+    if (b->ntcb == 0 || b->ntcb > RXG_FS_MAX_NTCB) return fail(-EINVAL, "rxg_flow_sums_dev: ntcb %u", b->ntcb);
+    if (b->flags & ~RXG_FS_TCP_OK_ONLY) return fail(-EINVAL, "rxg_flow_sums_dev: unknown flags 0x%x", b->flags);
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->out & 7u) || ((uintptr_t)b->count & 7u) ||
+        ((uintptr_t)b->off64 & 3u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align(b->rec_kind) - 1u)))
+        return fail(-EINVAL, "rxg_flow_sums_dev: frames need 16-byte, out and count 8-byte, off64 4-byte, len 2-byte, "
+                             "recs %u-byte alignment", (unsigned)rec_align(b->rec_kind));
+    int rc = reads_frames ? check_frame_src("rxg_flow_sums_dev", b->off64, b->slot0, b->stride64, b->n) : 0;
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchFlowSum L;
+    L.src = FrameSrc{reads_frames ? (const uint8_t *)b->frames : nullptr, b->off64, b->len, b->slot0, b->stride64};
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.ntcb = b->ntcb;
+    L.flags = b->flags;
+    L.out = b->out;
+    L.cap = b->cap;
+    L.count = (unsigned long long *)b->count;
+    L.acc = nullptr;
+    L.bits = nullptr;
+    L.tiles = nullptr;
+    L.max_blocks = c->max_blocks;
+    // (the accumulation's own grid; launch_flow_sum applies max_blocks on top of it)
+    L.acc_blocks = c->op_grid[kGridFlowSum] ? c->op_grid[kGridFlowSum] : 1024u;
+    if (b->n) {
+        DevBuf &acc = c->fs.buf[rxg_ctx::kFsAcc], &bits = c->fs.buf[rxg_ctx::kFsBits],
+               &tiles = c->fs.buf[rxg_ctx::kFsTiles];
+        if ((rc = c->fs.grow(acc, flow_sum_bytes(b->ntcb), true, st))) return rc;
+        if ((rc = c->fs.grow(bits, flow_sum_bits_bytes(b->ntcb), true, st))) return rc;
+        if ((rc = c->fs.grow(tiles, flow_sum_tile_bytes(b->ntcb), false, st))) return rc;
+        if ((rc = c->fs.begin(st))) return rc;
+        if (c->fs_dirty) {
+            HIP_OK(hipMemsetAsync(acc.p, 0, acc.bytes, st));
+            HIP_OK(hipMemsetAsync(bits.p, 0, bits.bytes, st));
+            c->fs_dirty = false;
+        }
+        L.acc = (FlowSumAcc *)acc.p;
+        L.bits = (uint32_t *)bits.p;
+        L.tiles = (uint32_t *)tiles.p;
+    }
+    const hipError_t e = launch_flow_sum(L, st);
+    if (b->n && e != hipSuccess) c->fs_dirty = true;
+    return c->fs.end(st, e);
+}

@@ -30,6 +30,7 @@
 //
 // Roofline: HBM, algorithmic bytes per frame = 2 x payload (read + write) + 16 (record)
 // + 16 (message descriptor).
+#include "rxg_dev.h"
 #include "rxg_kernels.h"
 
 namespace rxg {
@@ -75,28 +76,23 @@ __device__ __forceinline__ Cand candidate(const PgArgs &a, uint32_t i)
     if (i >= a.n) return c;
     // the record, the descriptor and the length are loaded together (one HBM round trip
     // before the frame's header word, not two)
-    // rxg_rec16: x tcb_idx | y checksums | z verdict, state<<8, tcp_flags<<16, flags<<24 | w datalen
-    // rxg_rec8 (stride 8): w0 verdict at 24 | w1 flags at 8, datalen + 128 at 14
-    uint32_t verdict, rflags;
-    int32_t datalen;
+    RecFields f;  // (rxg_dev.h: the words' layout)
     uint32_t off, flen;
     if (a.stride == 8u) {
         const uint2 r = *reinterpret_cast<const uint2 *>(a.recs + (size_t)i * 8u);
         off = a.off64[i];
         flen = a.len[i];
         asm volatile("" ::"v"(off), "v"(flen));
-        verdict = (r.x >> 24) & 7u;
-        rflags = (r.y >> 8) & 0x3Fu;
-        datalen = (int32_t)((r.y >> 14) & 0x1FFFFu) - 128;
+        f = rec8_fields(r);
     } else {
         const uint4 r = *reinterpret_cast<const uint4 *>(a.recs + (size_t)i * a.stride);
         off = a.off64[i];
         flen = a.len[i];
         asm volatile("" ::"v"(off), "v"(flen));  // keeps the two loads above the branch
-        verdict = r.z & 0xFFu;
-        rflags = r.z >> 24;
-        datalen = (int32_t)r.w;
+        f = rec16_fields(r);
     }
+    const uint32_t verdict = f.verdict, rflags = f.flags;
+    const int32_t datalen = f.datalen;
     if (verdict > RXG_V_RST_LISTEN_NONSYN || datalen <= 0 || (rflags & RXG_F_TRUNC)) return c;
     const uint64_t base = (uint64_t)off * 64u;
     // bytes 44..47 of the frame (>= 54 bytes: not RXG_F_TRUNC); data_off is byte 46
@@ -110,8 +106,10 @@ __device__ __forceinline__ Cand candidate(const PgArgs &a, uint32_t i)
     return c;
 }
 
+// Inclusive scan over the wave in its __shfl_up form (rxg_dev.h's wave_incl_scan is the
+// ds_bpermute ladder: swapping it in changes this file's code, which is left as measured).
 template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v, int lane)
+__device__ __forceinline__ T shfl_incl_scan(T v, int lane)
 {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -119,38 +117,6 @@ __device__ __forceinline__ T wave_incl_scan(T v, int lane)
         if (lane >= d) v += o;
     }
     return v;
-}
-
-__device__ __forceinline__ uint4 bperm16(uint4 v, int src_lane)
-{
-    uint4 r;
-    r.x = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v.x);
-    r.y = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v.y);
-    r.z = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v.z);
-    r.w = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v.w);
-    return r;
-}
-
-// bytes [sh, sh + 16) of the 32-byte string lo || hi
-__device__ __forceinline__ uint4 funnel16(uint4 lo, uint4 hi, uint32_t sh)
-{
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t ds = sh >> 2, bs = sh & 3u;
-    uint32_t s[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t)
-        s[t] = ds == 0 ? w[t] : ds == 1 ? w[t + 1] : ds == 2 ? w[t + 2] : w[t + 3];
-    uint4 r;
-    r.x = __builtin_amdgcn_alignbyte(s[1], s[0], bs);
-    r.y = __builtin_amdgcn_alignbyte(s[2], s[1], bs);
-    r.z = __builtin_amdgcn_alignbyte(s[3], s[2], bs);
-    r.w = __builtin_amdgcn_alignbyte(s[4], s[3], bs);
-    return r;
-}
-
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
-{
-    return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
 }
 
 // Copy phase of pg_copy: lane-per-chunk.  A wave takes its 256 frames in batches of 64;
@@ -283,7 +249,7 @@ __device__ __forceinline__ void copy_batch_pre(const PgArgs &a, WaveCopy &W, uin
     }
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vm, 0u));
     const uint32_t nch = valid ? (L + 15u) >> 4 : 0u;
-    const uint32_t incl = wave_incl_scan(nch, lane);
+    const uint32_t incl = shfl_incl_scan(nch, lane);
     const uint32_t start = incl - nch;
     const uint32_t T = (uint32_t)__shfl(incl, 63, 64);
     if (valid) {
@@ -393,7 +359,7 @@ __global__ __launch_bounds__(kPgFrames) void pg_gather(PgArgs a)
 
     const Cand c = candidate(a, i0);
     const uint32_t mine = (c.len + 15u) >> 4;
-    const uint32_t incl = wave_incl_scan(mine, lane);
+    const uint32_t incl = shfl_incl_scan(mine, lane);
     if (lane == 63) s_w[w] = incl;
     __syncthreads();
     uint32_t agg = 0, wex = 0;

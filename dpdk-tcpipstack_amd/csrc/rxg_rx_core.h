@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "rxg_common.h"
+#include "rxg_dev.h"  // lane_read, u32x4; rxg_rx_frames.h: dpp_down, group_sum
 #include "rxg_kernels.h"
 #include "rxg_mirror.h"
 
@@ -31,13 +32,6 @@ __device__ __forceinline__ uint32_t keep_low(uint32_t d, int keep)
 {
     return keep >= 4 ? d : (keep <= 0 ? 0u : (d & ((1u << (8 * keep)) - 1u)));
 }
-
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src_lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 template <bool NT>
 __device__ __forceinline__ uint4 load16(const uint8_t *p)

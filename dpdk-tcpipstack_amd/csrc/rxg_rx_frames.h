@@ -265,7 +265,7 @@ constexpr int class_min_len(int c)
 //  * loads need no clamp where every frame of the class is long enough (class minimum
 //    length, rounded up to its 64-byte line, which is readable); the others clamp to the
 //    frame's last chunk.
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+// (rxg_dev.h: dpp_down<K>, group_sum<LPF>)
 
 // acc + lo16(x) + hi16(x) (w = 0x00010001) or acc (w = 0)
 __device__ __forceinline__ uint32_t dsum(uint32_t x, uint32_t w, uint32_t acc)
@@ -273,26 +273,6 @@ __device__ __forceinline__ uint32_t dsum(uint32_t x, uint32_t w, uint32_t acc)
     return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, x), __builtin_bit_cast(u16x2, w), acc, false);
 }
 constexpr uint32_t kOnes = 0x00010001u;
-
-// lane l <- lane l + K of the same row of 16 lanes (0 past the row's end)
-template <int K>
-__device__ __forceinline__ uint32_t dpp_down(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + K, 0xF, 0xF, false);
-}
-
-// Sum of a group of LPF lanes (aligned at a multiple of LPF), valid in the group's first lane.
-template <int LPF>
-__device__ __forceinline__ uint32_t group_sum(uint32_t t, int lane)
-{
-    if constexpr (LPF >= 2) t += dpp_down<1>(t);
-    if constexpr (LPF >= 4) t += dpp_down<2>(t);
-    if constexpr (LPF >= 8) t += dpp_down<4>(t);
-    if constexpr (LPF >= 16) t += dpp_down<8>(t);
-    if constexpr (LPF >= 64) t += lane_read(t, (lane + 32) & 63);  // rows 0+2, 1+3
-    if constexpr (LPF >= 32) t += lane_read(t, (lane + 16) & 63);
-    return t;
-}
 
 // Adds the chunk's bytes [0, n), n < 16, to the four per-dword accumulators (bytes at or
 // past n read as zero).  Four accumulators: consecutive v_dot2 on one accumulator need a

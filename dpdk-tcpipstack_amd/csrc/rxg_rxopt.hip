@@ -27,52 +27,22 @@
 // Roofline: HBM, algorithmic bytes = n * record size + 6 n (off64 + len; 2 n in strided
 // mode) + per candidate the 64-byte lines that hold bytes 32 .. 54 + O and lie inside the
 // frame (64 or 128) + 16 n written.
+#include "rxg_dev.h"
 #include "rxg_kernels.h"
 
 namespace rxg {
 namespace {
 
 struct RoArgs {
-    const uint8_t *frames;
-    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
-    const uint16_t *len;
+    FrameSrc src;
     const uint8_t *recs;
     uint8_t *out;
-    uint32_t n, nslices, rec_kind, slot0, stride64;
+    uint32_t n, nslices, rec_kind;
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint4 ld16(const uint8_t *p)
-{
-    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ uint32_t ld4(const uint8_t *p)
-{
-    return __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p));
-}
-
-__device__ __forceinline__ void st16(uint8_t *p, uint4 o)
-{
-    u32x4 v;
-    v.x = o.x; v.y = o.y; v.z = o.z; v.w = o.w;
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
-}
-
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
-{
-    return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
-}
-
-// The verdict in frame i's record: rxg_rec8 w0 bits 24-26, rxg_rec16 / rxg_rec48 byte 8.
 __device__ __forceinline__ bool is_candidate(const RoArgs &a, uint32_t i)
 {
-    const uint8_t *r = a.recs + (size_t)i * a.rec_kind;
-    const uint32_t v = a.rec_kind == RXG_REC8 ? (*reinterpret_cast<const uint32_t *>(r) >> 24) & 7u
-                                              : *reinterpret_cast<const uint32_t *>(r + 8) & 0xFFu;
-    return v <= RXG_V_RST_LISTEN_NONSYN;
+    return rec_verdict(a.recs, a.rec_kind, i) <= RXG_V_RST_LISTEN_NONSYN;
 }
 
 // The option bytes as eleven dwords: b[j] is byte j & 3 of o[j >> 2], o[10] is zero.
@@ -136,11 +106,11 @@ __global__ __launch_bounds__(256) void rx_opts_parse(RoArgs a)
         const bool in = i < a.n;
         const bool cand = in && is_candidate(a, i);
         uint32_t ln = 0;
-        const uint8_t *f = a.frames;
+        const uint8_t *f = a.src.frames;
         if (cand) {
-            const uint32_t off = a.off64 ? a.off64[i] : a.slot0 + i * a.stride64;
-            ln = a.len[i];
-            f = a.frames + (size_t)off * 64u;  // 64-bit: a pool may pass 4 GiB
+            const uint32_t off = frame_slot(a.src, i);
+            ln = a.src.len[i];
+            f = a.src.frames + (size_t)off * 64u;  // 64-bit: a pool may pass 4 GiB
         }
         // every load below lies in a line that holds a frame byte below len
         uint32_t w44 = 0;
@@ -199,17 +169,7 @@ int rx_opts_blocks_per_cu()
 hipError_t launch_rx_opts(const LaunchRxOpts &R, hipStream_t st)
 {
     if (R.n == 0) return hipSuccess;
-    RoArgs a;
-    a.frames = R.frames;
-    a.off64 = R.off64;
-    a.len = R.len;
-    a.recs = R.recs;
-    a.out = R.out;
-    a.n = R.n;
-    a.nslices = (uint32_t)(((uint64_t)R.n + 63u) / 64u);
-    a.rec_kind = R.rec_kind;
-    a.slot0 = R.slot0;
-    a.stride64 = R.stride64;
+    const RoArgs a = {R.src, R.recs, R.out, R.n, (uint32_t)(((uint64_t)R.n + 63u) / 64u), R.rec_kind};
     uint32_t blocks = (a.nslices + 3u) / 4u;
     if (R.max_blocks && blocks > R.max_blocks) blocks = R.max_blocks;
     hipLaunchKernelGGL(rx_opts_parse, dim3(blocks), dim3(256), 0, st, a);

@@ -56,6 +56,7 @@
 // 64 * ceil((H + data_len) / 64) written.
 #include <type_traits>
 
+#include "rxg_dev.h"
 #include "rxg_kernels.h"
 
 namespace rxg {
@@ -97,82 +98,7 @@ struct Seg {
     uint32_t m0, m1, m2;  // frame bytes 0-11: dst MAC, src MAC
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint4 ld16(const uint8_t *p)
-{
-    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ void st16(uint8_t *p, uint4 o)
-{
-    u32x4 v;
-    v.x = o.x; v.y = o.y; v.z = o.z; v.w = o.w;
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
-}
-
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src_lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
-
 __device__ __forceinline__ uint32_t hsum(uint32_t d) { return (d & 0xFFFFu) + (d >> 16); }
-
-// acc + lo16(x) + hi16(x)  (rxg_rx_frames.h dsum)
-__device__ __forceinline__ uint32_t dsum(uint32_t x, uint32_t acc)
-{
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, x), __builtin_bit_cast(u16x2, 0x00010001u), acc, false);
-}
-
-// lane l <- lane l + K of the same row of 16 lanes (0 past the row's end)
-template <int K>
-__device__ __forceinline__ uint32_t dpp_down(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + K, 0xF, 0xF, false);
-}
-
-// Sum of a group of LPF lanes (aligned at a multiple of LPF), valid in the group's first lane
-// (rxg_rx_frames.h group_sum).
-template <int LPF>
-__device__ __forceinline__ uint32_t group_sum(uint32_t t, int lane)
-{
-    if constexpr (LPF >= 2) t += dpp_down<1>(t);
-    if constexpr (LPF >= 4) t += dpp_down<2>(t);
-    if constexpr (LPF >= 8) t += dpp_down<4>(t);
-    if constexpr (LPF >= 16) t += dpp_down<8>(t);
-    if constexpr (LPF >= 64) t += lane_read(t, (lane + 32) & 63);  // rows 0+2, 1+3
-    if constexpr (LPF >= 32) t += lane_read(t, (lane + 16) & 63);
-    return t;
-}
-
-// bytes [sh, sh + 16) of the 32-byte string lo || hi (rxg_payload.hip funnel16)
-__device__ __forceinline__ uint4 funnel16(uint4 lo, uint4 hi, uint32_t sh)
-{
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t ds = sh >> 2, bs = sh & 3u;
-    uint32_t s[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t)
-        s[t] = ds == 0 ? w[t] : ds == 1 ? w[t + 1] : ds == 2 ? w[t + 2] : w[t + 3];
-    uint4 r;
-    r.x = __builtin_amdgcn_alignbyte(s[1], s[0], bs);
-    r.y = __builtin_amdgcn_alignbyte(s[2], s[1], bs);
-    r.z = __builtin_amdgcn_alignbyte(s[3], s[2], bs);
-    r.w = __builtin_amdgcn_alignbyte(s[4], s[3], bs);
-    return r;
-}
-
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
-{
-    return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
-}
-
-__device__ __forceinline__ uint32_t drop_bytes(uint32_t v, int nb)
-{
-    return nb >= 4 ? 0u : nb <= 0 ? v : (v & ~((1u << (8 * nb)) - 1u));
-}
 
 // The option bytes of a segment (OPT; 0 otherwise) and its headers' length.
 template <bool OPT>
@@ -485,7 +411,7 @@ __global__ __launch_bounds__(256) void tx_build_kernel(Args<OPT> a)
             g.ports = f0.x; g.ip_src_raw = f0.y;
             g.ip_dst_host = f1.x; g.m0 = f1.y;
             g.m1 = f2.x; g.m2 = f2.y;
-            g.off = a.off64 ? a.off64[i] : a.slot0 + i * a.stride64;
+            g.off = frame_slot(a.off64, a.slot0, a.stride64, i);
         }
         if (inb) a.len[i] = valid ? (uint16_t)(kHdr + O + L) : (uint16_t)0;
         built += (uint32_t)__popcll(__ballot(valid));

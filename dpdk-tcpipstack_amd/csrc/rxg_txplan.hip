@@ -26,6 +26,7 @@
 // (next_seq) written, per segment 32 written.  The offsets pass (16 per send) and the expand
 // pass's search and send reads (served by the caches: neighbouring lanes read the same sends)
 // come on top.
+#include "rxg_dev.h"
 #include "rxg_kernels.h"
 
 namespace rxg {
@@ -89,24 +90,9 @@ __device__ __forceinline__ uint32_t cut_len(const TpArgs &a, uint32_t k)
     return a.mss > O ? a.mss - O : 0u;
 }
 
-__device__ __forceinline__ unsigned long long lane_read64(unsigned long long v, int src_lane)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)(uint32_t)(v >> 32));
-    return (unsigned long long)lo | ((unsigned long long)hi << 32);
-}
-
-// inclusive scan over the wave's 64 lanes
-__device__ __forceinline__ unsigned long long wave_scan(unsigned long long v, uint32_t lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = lane_read64(v, (int)((lane - (uint32_t)d) & 63u));
-        if (lane >= (uint32_t)d) v += up;
-    }
-    return v;
-}
-
+// Both scans below are the workgroup step of rxg_dev.h's block_scan with a second channel riding
+// on its two barriers (the refused sends).  Written out: as two block_scan calls the planner
+// measured 58.1 us against 57.1 on 2^20 one-segment sends, outside the runs' 0.7 us spread.
 __global__ __launch_bounds__(kTile) void tx_plan_count(TpArgs a)
 {
     __shared__ unsigned long long wsum[kTile / 64];
@@ -127,7 +113,7 @@ __global__ __launch_bounds__(kTile) void tx_plan_count(TpArgs a)
                                         : s.next_seq + s.bytes + ((s.flags & RXG_TCP_FLAG_SYN) ? 1u : 0u) +
                                               ((s.flags & RXG_TCP_FLAG_FIN) ? 1u : 0u);
         }
-        const unsigned long long inc = wave_scan(nseg, lane);
+        const unsigned long long inc = wave_incl_scan<unsigned long long>(nseg, lane);
         const unsigned long long rm = __ballot(refused);
         if (lane == 63u) {
             wsum[wave] = inc;
@@ -160,7 +146,7 @@ __global__ __launch_bounds__(kScanLanes) void tx_plan_scan(TpArgs a)
         const uint32_t e = base + threadIdx.x;  // (ntiles <= 2^24: no wrap)
         ulonglong2 v = make_ulonglong2(0ull, 0ull);
         if (e < a.ntiles) v = a.tiles[e];
-        const unsigned long long inc = wave_scan(v.x, lane), rinc = wave_scan(v.y, lane);
+        const unsigned long long inc = wave_incl_scan(v.x, lane), rinc = wave_incl_scan(v.y, lane);
         if (lane == 63u) {
             wsum[wave] = inc;
             wref[wave] = rinc;

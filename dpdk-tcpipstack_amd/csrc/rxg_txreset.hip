@@ -28,77 +28,27 @@
 //
 // Roofline: HBM, algorithmic bytes = 2 * n * record size (the records are read by the count
 // and by the build pass) + per reset 64 (read) + 64 (written) + 4 (idx).
+#include "rxg_dev.h"
 #include "rxg_kernels.h"
 
 namespace rxg {
 namespace {
 
 struct TrArgs {
-    const uint8_t *frames;
-    const uint32_t *off64;  // nullptr: frame i at slot slot0 + i * stride64
-    const uint16_t *len;
+    FrameSrc src;
     const uint8_t *recs;
     uint8_t *out;
     uint32_t *idx;
     unsigned long long cap;
     uint32_t *counts;       // nslices entries: the count pass's counts, then their prefix sums
-    uint32_t n, nslices, rec_kind, slot0, stride64;
+    uint32_t n, nslices, rec_kind;
     uint32_t ip_id0;
     uint32_t m0, m1;        // src_mac bytes 0-3, 4-5
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint4 ld16(const uint8_t *p)
-{
-    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ void st16(uint8_t *p, uint4 o)
-{
-    u32x4 v;
-    v.x = o.x; v.y = o.y; v.z = o.z; v.w = o.w;
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
-}
-
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src_lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
-
-// acc + lo16(x) + hi16(x)  (rxg_rx_frames.h dsum)
-__device__ __forceinline__ uint32_t dsum(uint32_t x, uint32_t acc)
-{
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, x), __builtin_bit_cast(u16x2, 0x00010001u), acc, false);
-}
-
-// lane l <- lane l + K of the same row of 16 lanes (0 past the row's end)
-template <int K>
-__device__ __forceinline__ uint32_t dpp_down(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + K, 0xF, 0xF, false);
-}
-
-// every lane of a group of 4 <- the group's lane Q (DPP quad_perm {Q, Q, Q, Q})
-template <int Q>
-__device__ __forceinline__ uint32_t quad_bcast(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, Q * 0x55, 0xF, 0xF, false);
-}
-
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int nb)
-{
-    return nb >= 4 ? v : nb <= 0 ? 0u : (v & ((1u << (8 * nb)) - 1u));
-}
-
-// The verdict in frame i's record: rxg_rec8 w0 bits 24-26, rxg_rec16 / rxg_rec48 byte 8.
 __device__ __forceinline__ bool is_rst(const TrArgs &a, uint32_t i)
 {
-    const uint8_t *r = a.recs + (size_t)i * a.rec_kind;
-    const uint32_t v = a.rec_kind == RXG_REC8 ? (*reinterpret_cast<const uint32_t *>(r) >> 24) & 7u
-                                              : *reinterpret_cast<const uint32_t *>(r + 8) & 0xFFu;
+    const uint32_t v = rec_verdict(a.recs, a.rec_kind, i);
     return v == RXG_V_RST_NOPCB || v == RXG_V_RST_LISTEN_NONSYN;
 }
 
@@ -120,7 +70,6 @@ constexpr uint32_t kScanLanes = 1024, kScanPer = 16;
 __global__ __launch_bounds__(1024) void tx_reset_scan(uint32_t *counts, uint32_t nslices, unsigned long long *count)
 {
     __shared__ uint32_t wsum[kScanLanes / 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t carry = 0;
     for (uint32_t base = 0; base < nslices; base += kScanLanes * kScanPer) {
         const uint32_t e0 = base + threadIdx.x * kScanPer;
@@ -139,25 +88,9 @@ __global__ __launch_bounds__(1024) void tx_reset_scan(uint32_t *counts, uint32_t
                 t += v[j];
             }
         }
-        // inclusive scan of t over the wave, then over the workgroup's waves
-        uint32_t inc = t;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = lane_read(inc, (int)((lane - (uint32_t)d) & 63u));
-            if (lane >= (uint32_t)d) inc += up;
-        }
-        if (lane == 63u) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kScanLanes / 64u; ++w) {
-            const uint32_t x = wsum[w];
-            if (w < wave) before += x;
-            total += x;
-        }
-        __syncthreads();  // wsum is rewritten by the next round
+        const BlockScan<uint32_t> b = block_scan<uint32_t, kScanLanes>(t, wsum);
         if (e0 < nslices) {
-            uint32_t run = carry + before + inc - t;
+            uint32_t run = carry + b.before + b.inc - t;
             uint4 *p = reinterpret_cast<uint4 *>(counts + e0);
 #pragma unroll
             for (uint32_t q = 0; q < kScanPer / 4u; ++q) {
@@ -169,7 +102,7 @@ __global__ __launch_bounds__(1024) void tx_reset_scan(uint32_t *counts, uint32_t
                 p[q] = w;
             }
         }
-        carry += total;
+        carry += b.total;
     }
     if (threadIdx.x == 0u) *count = carry;
 }
@@ -231,8 +164,8 @@ __global__ __launch_bounds__(256) void tx_reset_build(TrArgs a)
         const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         uint32_t off = 0, ln = 0;
         if (rst) {
-            off = a.off64 ? a.off64[i] : a.slot0 + i * a.stride64;
-            ln = a.len[i];
+            off = frame_slot(a.src, i);
+            ln = a.src.len[i];
             if ((unsigned long long)base + below < a.cap) a.idx[(size_t)base + below] = i;
         }
         // the slice's RST lanes compacted to 0 .. cnt-1, keeping their order
@@ -250,7 +183,7 @@ __global__ __launch_bounds__(256) void tx_reset_build(TrArgs a)
             const bool act = k < cnt && K < a.cap;  // uniform over the group
             uint4 in = make_uint4(0u, 0u, 0u, 0u);
             if (act && c < 3u) {
-                in = ld16(a.frames + (size_t)goff * 64u + 16u * c);
+                in = ld16(a.src.frames + (size_t)goff * 64u + 16u * c);
                 const int vb = glen - (int)(16u * c);  // bytes at and beyond len read as zero
                 if (vb < 16) {
                     in.x = keep_bytes(in.x, vb);
@@ -297,9 +230,7 @@ hipError_t launch_tx_reset(const LaunchTxReset &R, hipStream_t st)
 {
     if (R.n == 0) return hipMemsetAsync(R.count, 0, sizeof(unsigned long long), st);
     TrArgs a;
-    a.frames = R.frames;
-    a.off64 = R.off64;
-    a.len = R.len;
+    a.src = R.src;
     a.recs = R.recs;
     a.out = R.out;
     a.idx = R.idx;
@@ -308,8 +239,6 @@ hipError_t launch_tx_reset(const LaunchTxReset &R, hipStream_t st)
     a.n = R.n;
     a.nslices = (uint32_t)(((uint64_t)R.n + 63u) / 64u);
     a.rec_kind = R.rec_kind;
-    a.slot0 = R.slot0;
-    a.stride64 = R.stride64;
     a.ip_id0 = R.ip_id0;
     a.m0 = (uint32_t)R.src_mac[0] | ((uint32_t)R.src_mac[1] << 8) | ((uint32_t)R.src_mac[2] << 16) |
            ((uint32_t)R.src_mac[3] << 24);
