@@ -3,7 +3,8 @@
 //   rxg_host.cpp    context, TCB / ARP mirrors, launched bursts, counters, and
 //                   HipTablePort, the device side of rxg_tablesync.h
 //   rxg_ops.cpp     the operations on a burst beside its classification: tx checksums, segment
-//                   build, reset build, transmit planner, received options, flow summary
+//                   build, reset build, transmit planner, received options, flow summary,
+//                   flow trains
 //   rxg_tablesync.h the device tables and the order of their writes against the kernels that
 //                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
@@ -140,7 +141,8 @@ struct SerialScratch {
 };
 
 // The operations whose launch grid the context works out once, at init (rxg_ctx::op_grid).
-enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridOps };
+enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridFlowTrain,
+              kGridOps };
 
 struct rxg_ctx {
     int device = 0;
@@ -246,6 +248,16 @@ struct rxg_ctx {
     // (cleared when it returns); rxg_flow_sum_current answers from it
     const rxg_flow_sum *fs_host = nullptr;
     uint64_t fs_m = 0;
+
+    // rxg_flow_trains_dev: the pairs' two buffers, the segments' meta and the trains' starts, and
+    // the counts its launches hand on (buf[kFtPairs .. kFtCounts]); no content is kept
+    enum { kFtPairs, kFtMeta, kFtCounts };
+    SerialScratch ft{"rxg_flow_trains_dev"};
+    // rxg_flow_trains_attach: host copies of a call's order and trains for the replay that
+    // follows (cleared when it returns); rxg_flow_train_current answers from them
+    const uint32_t *ft_order = nullptr;
+    const rxg_flow_train *ft_trains = nullptr;
+    uint64_t ft_nseg = 0, ft_ntrains = 0;
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;

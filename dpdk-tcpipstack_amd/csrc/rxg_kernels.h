@@ -273,6 +273,35 @@ hipError_t launch_flow_sum(const LaunchFlowSum &F, hipStream_t st);
 size_t flow_sum_bytes(uint32_t ntcb);
 size_t flow_sum_bits_bytes(uint32_t ntcb);
 size_t flow_sum_tile_bytes(uint32_t ntcb);
+// rxg_flowtrain.hip: a burst's data segments grouped by flow and cut into trains
+// (rxg_flow_trains_dev): the select, the radix sort's passes and the cut on `st` (n == 0:
+// count = {0, 0, 0, 0} only)
+constexpr uint32_t kFtTile = 1024;         // pairs per tile of the sort and of the cut (a workgroup's)
+constexpr uint32_t kFtScanLanes = 1024;    // lanes of the one-workgroup scans
+constexpr uint32_t kFtScanPer = 16;        // entries per lane and round of a scan
+struct LaunchFlowTrain {
+    FrameSrc src;           // frames may be nullptr for RXG_REC48
+    uint32_t n;
+    uint32_t rec_kind;
+    const uint8_t *recs;
+    uint32_t ntcb, flags;
+    const uint32_t *cur_seq;    // may be nullptr
+    uint32_t *order;
+    unsigned long long cap_seg;
+    rxg_flow_train *trains;
+    unsigned long long cap_trains;
+    unsigned long long *count;  // 4 words
+    void *pairs;                // flow_train_pair_bytes(n) bytes, any content
+    void *meta;                 // flow_train_meta_bytes(n) bytes, any content
+    uint32_t *counts;           // flow_train_count_bytes(n) bytes, any content
+    uint32_t max_blocks;        // grid cap of every pass but the scans; 0 = 2^16
+};
+hipError_t launch_flow_train(const LaunchFlowTrain &F, hipStream_t st);
+uint32_t flow_train_passes(uint32_t ntcb);  // 8-bit passes of the sort: as many as ntcb - 1 has bytes
+size_t flow_train_pair_bytes(uint32_t n);
+size_t flow_train_meta_bytes(uint32_t n);
+size_t flow_train_count_bytes(uint32_t n);
+int flow_train_blocks_per_cu();  // resident 256-thread workgroups per CU of the scatter pass
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

@@ -1,8 +1,8 @@
 // rxg_ops.cpp — the operations on a burst beside its classification (include/rxg.h): tx
 // checksums, segment build with and without options, reset build, transmit planner,
-// received-option parse, flow summary.  Each entry point checks its arguments, fills its
-// kernels' launch struct (rxg_kernels.h) and launches on the caller's stream; what they share
-// -- rec_align, check_frame_src, grid_cap, SerialScratch -- is in rxg_ctx.h.
+// received-option parse, flow summary, flow trains.  Each entry point checks its arguments,
+// fills its kernels' launch struct (rxg_kernels.h) and launches on the caller's stream; what
+// they share -- rec_align, check_frame_src, grid_cap, SerialScratch -- is in rxg_ctx.h.
 #include <cstring>
 
 #include "rxg_ctx.h"
@@ -246,4 +246,56 @@ extern "C" int rxg_flow_sums_dev(rxg_ctx *c, const rxg_dev_flow_sums *b, void *s
     const hipError_t e = launch_flow_sum(L, st);
     if (b->n && e != hipSuccess) c->fs_dirty = true;
     return c->fs.end(st, e);
+}
+
+static_assert(sizeof(rxg_flow_train) == 32 && sizeof(rxg_dev_flow_trains) == 104, "flow train layouts");
+
+extern "C" int rxg_flow_trains_dev(rxg_ctx *c, const rxg_dev_flow_trains *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_flow_trains_dev: NULL argument");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_flow_trains_dev: rec_kind %u", b->rec_kind);
+    const bool reads_frames = b->rec_kind != RXG_REC48;
+    if (!b->recs || !b->count || (!b->order && b->cap_seg) || (!b->trains && b->cap_trains) ||
+        (reads_frames && (!b->frames || !b->len)))
+        return fail(-EINVAL, "rxg_flow_trains_dev: NULL device pointer");
+    if (b->ntcb == 0 || b->ntcb > RXG_FS_MAX_NTCB) return fail(-EINVAL, "rxg_flow_trains_dev: ntcb %u", b->ntcb);
+    if (b->flags & ~RXG_FT_TCP_OK_ONLY) return fail(-EINVAL, "rxg_flow_trains_dev: unknown flags 0x%x", b->flags);
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->trains & 7u) || ((uintptr_t)b->count & 7u) ||
+        ((uintptr_t)b->cur_seq & 3u) || ((uintptr_t)b->order & 3u) || ((uintptr_t)b->off64 & 3u) ||
+        ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align(b->rec_kind) - 1u)))
+        return fail(-EINVAL, "rxg_flow_trains_dev: frames need 16-byte, trains and count 8-byte, cur_seq, order and "
+                             "off64 4-byte, len 2-byte, recs %u-byte alignment", (unsigned)rec_align(b->rec_kind));
+    int rc = reads_frames ? check_frame_src("rxg_flow_trains_dev", b->off64, b->slot0, b->stride64, b->n) : 0;
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchFlowTrain L;
+    L.src = FrameSrc{reads_frames ? (const uint8_t *)b->frames : nullptr, b->off64, b->len, b->slot0, b->stride64};
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.ntcb = b->ntcb;
+    L.flags = b->flags;
+    L.cur_seq = b->cur_seq;
+    L.order = b->order;
+    L.cap_seg = b->cap_seg;
+    L.trains = b->trains;
+    L.cap_trains = b->cap_trains;
+    L.count = (unsigned long long *)b->count;
+    L.pairs = nullptr;
+    L.meta = nullptr;
+    L.counts = nullptr;
+    L.max_blocks = grid_cap(c, c->op_grid[kGridFlowTrain]);
+    if (b->n) {
+        DevBuf &pairs = c->ft.buf[rxg_ctx::kFtPairs], &meta = c->ft.buf[rxg_ctx::kFtMeta],
+               &counts = c->ft.buf[rxg_ctx::kFtCounts];
+        if ((rc = c->ft.grow(pairs, flow_train_pair_bytes(b->n), false, st))) return rc;
+        if ((rc = c->ft.grow(meta, flow_train_meta_bytes(b->n), false, st))) return rc;
+        if ((rc = c->ft.grow(counts, flow_train_count_bytes(b->n), false, st))) return rc;
+        if ((rc = c->ft.begin(st))) return rc;
+        L.pairs = pairs.p;
+        L.meta = meta.p;
+        L.counts = (uint32_t *)counts.p;
+    }
+    return c->ft.end(st, launch_flow_train(L, st));
 }

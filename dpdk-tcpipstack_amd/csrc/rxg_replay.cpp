@@ -223,6 +223,60 @@ extern "C" int rxg_flow_sum_current(rxg_ctx *c, const rxg_flow_sum **out, uint32
     return 1;
 }
 
+// ------------------------------------------------------------------- flow trains ---
+extern "C" int rxg_flow_trains_attach(rxg_ctx *c, const uint32_t *order_host, uint64_t nseg,
+                                      const rxg_flow_train *trains_host, uint64_t ntrains)
+{
+    if (!c || (nseg && !order_host) || (ntrains && !trains_host))
+        return fail(-EINVAL, "rxg_flow_trains_attach: NULL argument");
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < ntrains; ++k) {
+        const rxg_flow_train &t = trains_host[k];
+        if (t.first != at || t.nseg == 0 || (k && t.tcb_idx < trains_host[k - 1].tcb_idx))
+            return fail(-EINVAL, "rxg_flow_trains_attach: train %llu does not start where its predecessor ended "
+                                 "(first %u, nseg %u, expected first %llu)",
+                        (unsigned long long)k, t.first, t.nseg, (unsigned long long)at);
+        at += t.nseg;
+    }
+    c->ft_order = nseg ? order_host : nullptr;
+    c->ft_trains = ntrains ? trains_host : nullptr;
+    c->ft_nseg = nseg;
+    c->ft_ntrains = ntrains;
+    return 0;
+}
+
+// The packet being replayed, if its record is still the burst's (rp_seq 0: not re-classified)
+// and a DISPATCH: the attached trains of its flow are found by tcb_idx, the packet among the
+// flow's segments (ascending packet indices), and its train by that position.
+extern "C" int rxg_flow_train_current(rxg_ctx *c, const rxg_flow_train **out, uint32_t *pos_out)
+{
+    if (!c || !out || !pos_out) return fail(-EINVAL, "rxg_flow_train_current: NULL argument");
+    const int64_t pos = c->replay_pos;
+    if (pos < 0 || !c->ft_order || !c->ft_trains || (uint64_t)pos >= c->rp_cur.size() ||
+        (uint64_t)pos >= c->rp_seq.size())
+        return 0;
+    const rxg_rec16 &r = c->rp_cur[(size_t)pos];
+    if (c->rp_seq[(size_t)pos] != 0u || r.verdict != RXG_V_DISPATCH) return 0;
+    const rxg_flow_train *lo = c->ft_trains, *hi = c->ft_trains + c->ft_ntrains;
+    const rxg_flow_train *tl =
+        std::lower_bound(lo, hi, r.tcb_idx, [](const rxg_flow_train &e, int32_t t) { return e.tcb_idx < t; });
+    const rxg_flow_train *th =
+        std::upper_bound(tl, hi, r.tcb_idx, [](int32_t t, const rxg_flow_train &e) { return t < e.tcb_idx; });
+    if (tl == th) return 0;
+    const uint64_t a = tl->first, b = std::min<uint64_t>((uint64_t)(th - 1)->first + (th - 1)->nseg, c->ft_nseg);
+    if (a >= b) return 0;
+    const uint32_t *seg = std::lower_bound(c->ft_order + a, c->ft_order + b, (uint32_t)pos);
+    if (seg == c->ft_order + b || *seg != (uint32_t)pos) return 0;
+    const uint64_t q = (uint64_t)(seg - c->ft_order);
+    // the last train of the flow that starts at or before q
+    const rxg_flow_train *t =
+        std::upper_bound(tl, th, q, [](uint64_t v, const rxg_flow_train &e) { return v < e.first; }) - 1;
+    if ((uint64_t)t->first + t->nseg > c->ft_nseg) return 0;  // order was capped inside this train
+    *out = t;
+    *pos_out = (uint32_t)(q - t->first);
+    return 1;
+}
+
 // ------------------------------------------------------------------------- replay ---
 static inline bool rec_is_tcp(const rxg_rec16 &r)
 {
@@ -340,6 +394,9 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
             c->opt_live = false;
             c->fs_host = nullptr;
             c->fs_m = 0;
+            c->ft_order = nullptr;
+            c->ft_trains = nullptr;
+            c->ft_nseg = c->ft_ntrains = 0;
         }
     } pos_guard{c};
     if (!ops || (n && (!mbufs || !frames || !recs)))

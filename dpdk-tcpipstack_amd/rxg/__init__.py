@@ -11,6 +11,7 @@ The reference surface this mirrors (rajneshrat/dpdk-tcpipstack, tcp_ip_stack/):
   send_reset per offender (tcp_out.c:103-146) -> Engine.tx_reset_dev, reset_attach / reset_take
   (no counterpart: received TCP options)     -> Engine.rx_opts_dev, rx_opt_parse, rx_opts_attach / rx_opt_current
   on_segment's per-flow work (tcp_in.c:66-71) -> Engine.flow_sums_dev, flow_sums_host, flow_sums_attach / flow_sum_current
+  PushData on in-order segments (tcp_windows.c:341-358) -> Engine.flow_trains_dev, flow_trains_host, flow_trains_attach / flow_train_current
 """
 from __future__ import annotations
 
@@ -120,6 +121,21 @@ FS_MAX_NTCB = 1 << 24
 # per round of the scan (what the edge tests are named from)
 FLOW_SUM_TILE_TCBS = 2048
 FLOW_SUM_SCAN_TILES = 1024
+# a burst's data segments grouped by flow and cut into trains (rxg_flow_trains_dev,
+# rxg_flow_trains_host): rxg_flow_train and its RXG_FTR_* flags
+FLOW_TRAIN_DTYPE = np.dtype([("tcb_idx", "<i4"), ("first", "<u4"), ("nseg", "<u4"), ("seq", "<u4"), ("bytes", "<u8"),
+                             ("next_ack", "<u4"), ("flags", "<u4")])
+assert FLOW_TRAIN_DTYPE.itemsize == 32
+FTR_HEAD, FTR_FIN, FTR_WRAP, FTR_FLOW_FIRST, FTR_FLOW_LAST = 0x01, 0x02, 0x04, 0x08, 0x10
+FT_TCP_OK_ONLY = 1
+# csrc/rxg_kernels.h kFtTile / kFtScanLanes * kFtScanPer: pairs per tile of the sort and of the
+# cut (a workgroup takes a tile in rounds of 256 lanes, four waves each), entries per round of
+# the one-workgroup scans -- of slices (64 frames) in the select, of digit-by-tile counts (256
+# per tile) in a sort pass, of tiles in the cut (what the edge tests are named from)
+FLOW_TRAIN_TILE = 1024
+FLOW_TRAIN_ROUND_LANES = 256
+FLOW_TRAIN_SCAN_ROUND = 1024 * 16
+
 
 
 def rec8_pack(r16: np.ndarray) -> np.ndarray:
@@ -292,6 +308,14 @@ class DevFlowSums(C.Structure):
                 ("count", C.c_void_p)]
 
 
+class DevFlowTrains(C.Structure):
+    """rxg_dev_flow_trains."""
+    _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
+                ("stride64", C.c_uint32), ("n", C.c_uint32), ("rec_kind", C.c_uint32), ("recs", C.c_void_p),
+                ("ntcb", C.c_uint32), ("flags", C.c_uint32), ("cur_seq", C.c_void_p), ("order", C.c_void_p),
+                ("cap_seg", C.c_uint64), ("trains", C.c_void_p), ("cap_trains", C.c_uint64), ("count", C.c_void_p)]
+
+
 class PktView(C.Structure):
     _fields_ = [("buf_addr", C.c_void_p), ("data_off", C.c_uint16), ("data_len", C.c_uint16),
                 ("pad", C.c_uint32)]
@@ -418,6 +442,10 @@ def load_library(path: str = LIB_PATH):
         "rxg_flow_sums_host": (C.c_int, [vp, u32, vp, vp, u32, u32, u32, vp, u64, vp]),
         "rxg_flow_sums_attach": (C.c_int, [vp, vp, u64]),
         "rxg_flow_sum_current": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u32)]),
+        "rxg_flow_trains_dev": (C.c_int, [vp, C.POINTER(DevFlowTrains), vp]),
+        "rxg_flow_trains_host": (C.c_int, [vp, u32, vp, vp, u32, u32, u32, vp, vp, u64, vp, u64, vp]),
+        "rxg_flow_trains_attach": (C.c_int, [vp, vp, u64, vp, u64]),
+        "rxg_flow_train_current": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u32)]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -702,6 +730,38 @@ def flow_sums_host(recs, rec_kind: int, ntcb: int, frames=None, flags: int = 0, 
     if rc:
         raise RxgError(f"rxg_flow_sums_host failed ({rc})")
     return (buf if out is not None else buf[:min(int(count[0]), cap)].copy()), count
+
+
+def flow_trains_host(recs, rec_kind: int, ntcb: int, frames=None, flags: int = 0, cur_seq=None, cap_seg=None,
+                     cap_trains=None, order=None, trains=None):
+    """rxg_flow_trains_host: the burst's data segments grouped by flow and cut into trains, in host
+    memory.  recs / frames as flow_sums_host's; cur_seq: ntcb u32 or None.  Returns (order u32 of
+    min(count[0], cap_seg) entries, trains FLOW_TRAIN_DTYPE of min(count[1], cap_trains) entries,
+    count u64[4]); a cap of None: room for everything.  order / trains: arrays of at least the
+    caps' entries written in place (returned whole instead)."""
+    lib = load_library()
+    recs = np.ascontiguousarray(recs)
+    n = recs.nbytes // rec_kind if rec_kind in (REC8, REC16, REC48) else len(recs)
+    keep, ptrs, lens = [], None, None
+    if frames is not None:
+        keep = [C.create_string_buffer(bytes(f), max(len(f), 1)) for f in frames]
+        ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(x) for x in keep])
+        lens = np.array([len(f) for f in frames], np.uint16)
+    cs = None if cur_seq is None else np.ascontiguousarray(cur_seq, dtype=np.uint32)
+    if cs is not None and len(cs) < ntcb:
+        raise ValueError("flow_trains_host: cur_seq needs ntcb entries")
+    cap_seg = n if cap_seg is None else cap_seg
+    cap_trains = n if cap_trains is None else cap_trains
+    obuf = order if order is not None else np.zeros(max(cap_seg, 1), np.uint32)
+    tbuf = trains if trains is not None else np.zeros(max(cap_trains, 1), FLOW_TRAIN_DTYPE)
+    count = np.zeros(4, np.uint64)
+    rc = lib.rxg_flow_trains_host(_ptr(recs) if n else None, rec_kind, ptrs, None if lens is None else _ptr(lens), n,
+                                  ntcb, flags, None if cs is None else _ptr(cs), _ptr(obuf) if cap_seg else None,
+                                  cap_seg, _ptr(tbuf) if cap_trains else None, cap_trains, _ptr(count))
+    if rc:
+        raise RxgError(f"rxg_flow_trains_host failed ({rc})")
+    return (obuf if order is not None else obuf[:min(int(count[0]), cap_seg)].copy(),
+            tbuf if trains is not None else tbuf[:min(int(count[1]), cap_trains)].copy(), count)
 
 
 # -------------------------------------------------------------------------- engine ---
@@ -1061,6 +1121,32 @@ class Engine:
         rc = _lib.rxg_flow_sum_current(self.ctx, C.byref(p), C.byref(i))
         _check(min(rc, 0), "rxg_flow_sum_current")
         return (np.frombuffer(C.string_at(p.value, 40), dtype=FLOW_SUM_DTYPE)[0], i.value) if rc == 1 else None
+
+    def flow_trains_dev(self, recs: int, rec_kind: int, n: int, ntcb: int, order: int | None, cap_seg: int,
+                        trains: int | None, cap_trains: int, count: int, cur_seq: int | None = None,
+                        frames: int | None = None, lens: int | None = None, off64: int | None = None, slot0: int = 0,
+                        stride64: int = 0, flags: int = 0, stream=None):
+        """rxg_flow_trains_dev: the packet indices of the burst's data segments at order + 4 * k,
+        sorted by (tcb_idx, packet index), and one rxg_flow_train (FLOW_TRAIN_DTYPE) at trains +
+        32 * k per maximal in-order run; count (4 u64, written) = {segments, trains, DISPATCH
+        records outside [0, ntcb), frames left out by FT_TCP_OK_ONLY}.  All device addresses;
+        frames / lens may be None for REC48, cur_seq (ntcb u32) None for no HEAD trains."""
+        b = DevFlowTrains(frames, off64, lens, slot0, stride64, n, rec_kind, recs, ntcb, flags, cur_seq, order, cap_seg,
+                          trains, cap_trains, count)
+        _check(_lib.rxg_flow_trains_dev(self.ctx, C.byref(b), stream), "rxg_flow_trains_dev")
+
+    def flow_trains_attach(self, order_host: int, nseg: int, trains_host: int, ntrains: int):
+        """rxg_flow_trains_attach: host copies (addresses) of a flow_trains_dev call's order and trains
+        for the next rx replay; the caller keeps them alive until that replay returns."""
+        _check(_lib.rxg_flow_trains_attach(self.ctx, order_host, nseg, trains_host, ntrains), "rxg_flow_trains_attach")
+
+    def flow_train_current(self):
+        """Inside a replay's handler: (the FLOW_TRAIN_DTYPE train of the replayed packet (a copy),
+        the packet's position in it), or None (see rxg_flow_train_current)."""
+        p, i = C.c_void_p(), C.c_uint32()
+        rc = _lib.rxg_flow_train_current(self.ctx, C.byref(p), C.byref(i))
+        _check(min(rc, 0), "rxg_flow_train_current")
+        return (np.frombuffer(C.string_at(p.value, 32), dtype=FLOW_TRAIN_DTYPE)[0], i.value) if rc == 1 else None
 
     def tx_build(self, payload: np.ndarray, flows: np.ndarray, segs: np.ndarray, off64=None, slot0: int = 0,
                  stride64: int = 0, opts=None):

@@ -1016,6 +1016,144 @@ int rxg_flow_sums_attach(rxg_ctx *ctx, const rxg_flow_sum *sums_host, uint64_t m
 int rxg_flow_sum_current(rxg_ctx *ctx, const rxg_flow_sum **out, uint32_t *pkt_idx);
 
 /* ------------------------------------------------------------------------- */
+/* A burst's data segments grouped by flow and cut into in-order trains: which */
+/* segments of one connection follow each other in sequence space, and how far */
+/* they take that connection's stream (ptcb->ack after the burst,              */
+/* tcp_windows.c:355, the value AdjustPair returns).                           */
+/*                                                                             */
+/* Which frames are segments.  Frame i is a segment when its record's verdict  */
+/* is RXG_V_DISPATCH, 0 <= tcb_idx < ntcb, with RXG_FT_TCP_OK_ONLY its record  */
+/* carries RXG_F_TCP_OK, and 0 < datalen <= 65535 (what PushData's uint16_t    */
+/* Length can express, tcp_windows.c:341).  Counts, exactly as in              */
+/* rxg_flow_sums_dev: a DISPATCH record whose tcb_idx is outside [0, ntcb) is  */
+/* never followed and is counted in count[2]; a DISPATCH frame left out by the */
+/* checksum flag alone is counted in count[3]; everything else is ignored.     */
+/*                                                                             */
+/* Where the fields come from.  tcb_idx, datalen and tcp_flags come from the   */
+/* record (rxg_rec8 decoded as rxg_rec8_expand does).  seq is, for RXG_REC8    */
+/* and RXG_REC16, big-endian frame[38..42) with bytes at or beyond len[i] read */
+/* as zero; for RXG_REC48 it is the record's seq and no frame byte is read:    */
+/* frames, off64 and len may then be NULL (the flow summary's rule).           */
+/*                                                                             */
+/* Order.  order[0..S) holds the packet indices of the S segments sorted by    */
+/* (tcb_idx ascending, packet index ascending): a stable grouping, within a    */
+/* flow the segments stand in the order they arrived.                          */
+/*                                                                             */
+/* Trains.  Walk a flow's segments in that order.  Segment b continues segment */
+/* a, the one before it in the same flow, when seq_b == (uint32_t)(seq_a +     */
+/* datalen_a), a does not carry FIN, and neither a nor b is a wrapping         */
+/* segment.  A segment wraps when (uint64_t)seq + datalen >= 2^32: the         */
+/* reference's duplicate test `cur > seq + Length` (tcp_windows.c:350)         */
+/* compares a wrapped sum and drops such a segment, so a wrapping segment is   */
+/* always a train of its own and is flagged.  A train is a maximal run of      */
+/* continuing segments; trains are written in the order of `order`: train k's  */
+/* segments are order[first .. first + nseg).                                  */
+/*                                                                             */
+/* HEAD.  cur_seq is an optional array of ntcb words, the stack's              */
+/* ReceiveWindow.CurrentSequenceNumber per TCB; with NULL no train is HEAD.    */
+/* For a flow whose window holds no pairs and whose CurrentSequenceNumber is   */
+/* cur_seq[tcb_idx], a HEAD train's segments fed to the reference's PushData   */
+/* one at a time are none refused, each becomes one socket-ring message,       */
+/* whole; the messages concatenated are the train's payload bytes; ptcb->ack   */
+/* ends as next_ack and CurrentSequenceNumber as (uint32_t)(seq + bytes).  The */
+/* != 0 condition is GetData's assert (tcp_windows.c:151), as in               */
+/* rxg_payload_take.  Two deliberate cuts, both conservative: only a flow's    */
+/* first train can be HEAD, and a FIN ends its train although the reference's  */
+/* CurrentSequenceNumber does not count the FIN.  For every train that is not  */
+/* HEAD the stack runs its own PushData: the cuts cost speed, never            */
+/* correctness.                                                                */
+/*                                                                             */
+/* Outputs and caps.  order has cap_seg entries, trains cap_trains; entries at */
+/* or past a cap are not written.  count is 4 words, WRITTEN (not added to):   */
+/* segments S, trains T, DISPATCH out of range, left out; count[0] and         */
+/* count[1] are what the burst needs whatever the caps are (rxg_tx_reset_dev's */
+/* cap / *count rule).  A train is written whole or not at all, and its first  */
+/* and nseg are correct even if order was capped short of them.  n == 0 writes */
+/* count = {0, 0, 0, 0} and nothing else.  The output is a pure function of    */
+/* the arguments: never of the grid, the stream, the mirror or an earlier call.*/
+/* ------------------------------------------------------------------------- */
+typedef struct rxg_flow_train {   /* 32 bytes, arrays 8-byte aligned */
+    int32_t  tcb_idx;
+    uint32_t first;      /* its segments are order[first .. first + nseg)                    */
+    uint32_t nseg;
+    uint32_t seq;        /* ntohl(sent_seq) of its first segment                             */
+    uint64_t bytes;      /* sum of datalen over its segments                                 */
+    uint32_t next_ack;   /* (uint32_t)(seq + bytes) + (FIN ? 1 : 0): what AdjustPair returns */
+                         /* after the train has been delivered (tcp_windows.c:104-109)       */
+    uint32_t flags;      /* RXG_FTR_*                                                        */
+} rxg_flow_train;
+#define RXG_FTR_HEAD       0x01u /* the flow's first train, cur_seq given, cur_seq[tcb_idx] != 0 and == seq, not WRAP */
+#define RXG_FTR_FIN        0x02u /* its last segment carries FIN                               */
+#define RXG_FTR_WRAP       0x04u /* a single wrapping segment                                  */
+#define RXG_FTR_FLOW_FIRST 0x08u /* first / last train of its flow in this burst               */
+#define RXG_FTR_FLOW_LAST  0x10u
+#define RXG_FT_TCP_OK_ONLY 0x1u  /* leave out frames without RXG_F_TCP_OK (RXG_OPS_VERIFY_TCP_CKSUM stacks) */
+
+/* frames / off64 / len / slot0 / stride64 / recs / ntcb follow rxg_dev_flow_sums' rules (of a
+   segment only the 16 bytes at 32..47 are read, and only when len[i] > 38).  Asynchronous on
+   `stream`: a select (slice counts, their scan, a compaction into (tcb_idx, packet index)
+   pairs), a least-significant-digit radix sort of the pairs on tcb_idx (8 bits a pass; 1 pass
+   up to 256 TCBs, 2 up to 65 536, 3 above; each a per-tile digit count, a scan and a scatter
+   without atomics) and a cut (per-tile train starts, their scan, the start list, one lane per
+   train); no workgroup waits on another, and rxg_config.max_blocks caps the grids.  The
+   context owns the scratch (about 30 bytes per frame), grown on demand; one call at a time uses it:
+   a call on another stream waits (on the device, through an event) for the previous call on
+   this context.
+   -EINVAL: a NULL ctx, b, recs or count; order NULL with cap_seg != 0; trains NULL with
+   cap_trains != 0; frames or len NULL unless rec_kind is RXG_REC48; a bad rec_kind; ntcb 0 or
+   over RXG_FS_MAX_NTCB; unknown flag bits; frames not 16-, trains or count not 8-, cur_seq,
+   order or off64 not 4-, len not 2-byte aligned, recs not 8- (RXG_REC8) or 16-byte aligned;
+   where frames are read, stride64 0 or slot0 + (n - 1) * stride64 over 2^32 - 1 in strided
+   mode.  -ENOMEM: the scratch cannot be allocated; nothing is launched then.  A group's
+   members are plain contexts for this call. */
+typedef struct rxg_dev_flow_trains {
+    const void *frames;       /* dev: the burst's frame pool; may be NULL for RXG_REC48          */
+    const uint32_t *off64;    /* dev, n entries; NULL = fixed stride (slot0 + i * stride64)      */
+    const uint16_t *len;      /* dev, n entries; may be NULL for RXG_REC48                       */
+    uint32_t slot0, stride64; /* used when off64 == NULL                                         */
+    uint32_t n;
+    uint32_t rec_kind;        /* RXG_REC8 / RXG_REC16 / RXG_REC48                                */
+    const void *recs;         /* dev: the burst's n records, as the burst wrote them             */
+    uint32_t ntcb;            /* 1 .. RXG_FS_MAX_NTCB: TCB indices at or past it are not followed */
+    uint32_t flags;           /* RXG_FT_*                                                        */
+    const uint32_t *cur_seq;  /* dev, ntcb words, 4-byte aligned; NULL: no train is HEAD         */
+    uint32_t *order;          /* dev, 4-byte aligned, cap_seg entries                            */
+    uint64_t cap_seg;
+    rxg_flow_train *trains;   /* dev, 8-byte aligned, cap_trains entries                         */
+    uint64_t cap_trains;
+    uint64_t *count;          /* dev, 4 words, WRITTEN: segments, trains, out of range, left out */
+} rxg_dev_flow_trains;
+int rxg_flow_trains_dev(rxg_ctx *ctx, const rxg_dev_flow_trains *b, void *stream);
+
+/* Host form of the rule (no context, no GPU), for host-buffer bursts (rxg_rx_burst): frame i
+   is frames[i][0 .. len[i]); frames and len may be NULL for RXG_REC48; cur_seq is ntcb words
+   of host memory or NULL.  Returns 0; -EINVAL: recs or count NULL (n != 0 for recs), order
+   NULL with cap_seg != 0, trains NULL with cap_trains != 0, frames or len NULL unless
+   RXG_REC48 (n != 0), a bad rec_kind, ntcb 0 or over RXG_FS_MAX_NTCB, unknown flag bits;
+   -ENOMEM. */
+int rxg_flow_trains_host(const void *recs, uint32_t rec_kind, void *const *frames, const uint16_t *len,
+                         uint32_t n, uint32_t ntcb, uint32_t flags, const uint32_t *cur_seq, uint32_t *order,
+                         uint64_t cap_seg, rxg_flow_train *trains, uint64_t cap_trains, uint64_t count[4]);
+
+/* Using the trains during the replay.  rxg_flow_trains_attach names host copies of a call's
+   `order` (nseg = min(count[0], cap_seg) entries) and `trains` (ntrains = min(count[1],
+   cap_trains) entries) for the burst the next rxg_rx_replay call on this context replays; the
+   attachment ends when that replay returns, however it returns.  rxg_flow_train_current is
+   called from a handler (PushData's call site) while the replay runs a packet.  It returns 1,
+   with *out the packet's train and *pos its position in that train (order[first + *pos] is
+   the packet), when the packet is a segment of an attached train that lies whole inside the
+   attached order and the replay did not replace the packet's record by re-classification.
+   It returns 0 otherwise: outside a replay, with nothing attached, for a re-classified
+   packet, for a packet that is no segment, or for a segment or train past a cap.
+   -EINVAL: ctx, out or pos NULL (attach: ctx NULL, a NULL array with a nonzero length, or
+   trains that do not tile [0, nseg) in order: train k must start where train k - 1 ended,
+   train 0 at 0, nseg >= 1 each, tcb_idx never descending; trains whose segments lie past
+   nseg may follow). */
+int rxg_flow_trains_attach(rxg_ctx *ctx, const uint32_t *order_host, uint64_t nseg,
+                           const rxg_flow_train *trains_host, uint64_t ntrains);
+int rxg_flow_train_current(rxg_ctx *ctx, const rxg_flow_train **out, uint32_t *pos);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
