@@ -4,7 +4,7 @@
 //                   HipTablePort, the device side of rxg_tablesync.h
 //   rxg_ops.cpp     the operations on a burst beside its classification: tx checksums, segment
 //                   build, reset build, transmit planner, received options, flow summary,
-//                   flow trains
+//                   flow trains, train payload
 //   rxg_tablesync.h the device tables and the order of their writes against the kernels that
 //                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
@@ -142,7 +142,7 @@ struct SerialScratch {
 
 // The operations whose launch grid the context works out once, at init (rxg_ctx::op_grid).
 enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridFlowTrain,
-              kGridOps };
+              kGridTrainPay, kGridOps };
 
 struct rxg_ctx {
     int device = 0;
@@ -258,6 +258,8 @@ struct rxg_ctx {
     const uint32_t *ft_order = nullptr;
     const rxg_flow_train *ft_trains = nullptr;
     uint64_t ft_nseg = 0, ft_ntrains = 0;
+    // rxg_train_payload_dev: the trains' offsets and the tile sums (buf[0]); no content is kept
+    SerialScratch tp{"rxg_train_payload_dev"};
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;

@@ -302,6 +302,32 @@ size_t flow_train_pair_bytes(uint32_t n);
 size_t flow_train_meta_bytes(uint32_t n);
 size_t flow_train_count_bytes(uint32_t n);
 int flow_train_blocks_per_cu();  // resident 256-thread workgroups per CU of the scatter pass
+// rxg_trainpay.hip: a burst's payload gathered by train (rxg_train_payload_dev): msgs zeroed, the
+// taking trains' padded sizes per tile, their one-workgroup scan, the trains' offsets and the
+// copy on `st` (n == 0: *used = 0 only)
+constexpr uint32_t kTpTile = 256;        // trains per tile of the offsets, segments per tile of the copy
+constexpr uint32_t kTpScanLanes = 256;   // tile sums per round of the one-workgroup scan
+struct LaunchTrainPay {
+    FrameSrc src;
+    uint32_t n;
+    uint32_t rec_kind;
+    const uint8_t *recs;
+    const uint32_t *order;
+    unsigned long long cap_seg;
+    const rxg_flow_train *trains;
+    unsigned long long cap_trains;
+    const unsigned long long *count;  // the flow-train call's 4 words, read on the device
+    uint32_t flags;
+    uint8_t *arena;
+    unsigned long long arena_cap;
+    rxg_payload_msg *msgs, *tmsgs;    // either may be nullptr
+    unsigned long long *used;         // 1 entry
+    void *scratch;                    // train_pay_scratch_bytes(n, cap_trains) bytes, any content
+    uint32_t max_blocks;              // grid cap of every pass but the scan; 0 = 2^16
+};
+hipError_t launch_train_pay(const LaunchTrainPay &P, hipStream_t st);
+size_t train_pay_scratch_bytes(uint32_t n, unsigned long long cap_trains);
+int train_pay_blocks_per_cu();  // resident 256-thread workgroups per CU of the copy
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

@@ -1,6 +1,6 @@
 // rxg_ops.cpp — the operations on a burst beside its classification (include/rxg.h): tx
 // checksums, segment build with and without options, reset build, transmit planner,
-// received-option parse, flow summary, flow trains.  Each entry point checks its arguments,
+// received-option parse, flow summary, flow trains, train payload.  Each entry point checks its arguments,
 // fills its kernels' launch struct (rxg_kernels.h) and launches on the caller's stream; what
 // they share -- rec_align, check_frame_src, grid_cap, SerialScratch -- is in rxg_ctx.h.
 #include <cstring>
@@ -298,4 +298,65 @@ extern "C" int rxg_flow_trains_dev(rxg_ctx *c, const rxg_dev_flow_trains *b, voi
         L.counts = (uint32_t *)counts.p;
     }
     return c->ft.end(st, launch_flow_train(L, st));
+}
+
+static_assert(sizeof(rxg_dev_train_payload) == 136, "train payload layout");
+
+extern "C" int rxg_train_payload_dev(rxg_ctx *c, const rxg_dev_train_payload *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_train_payload_dev: NULL argument");
+    if (!rec_kind_ok(b->rec_kind)) return fail(-EINVAL, "rxg_train_payload_dev: rec_kind %u", b->rec_kind);
+    if (!b->frames || !b->len || !b->recs || !b->count || !b->arena_used || (!b->order && b->cap_seg) ||
+        (!b->trains && b->cap_trains) || (!b->arena && b->arena_cap))
+        return fail(-EINVAL, "rxg_train_payload_dev: NULL device pointer");
+    if (b->flags & ~RXG_TP_HEAD_ONLY) return fail(-EINVAL, "rxg_train_payload_dev: unknown flags 0x%x", b->flags);
+    if (((uintptr_t)b->frames & 15u) || ((uintptr_t)b->arena & 15u) || ((uintptr_t)b->msgs & 7u) ||
+        ((uintptr_t)b->tmsgs & 7u) || ((uintptr_t)b->trains & 7u) || ((uintptr_t)b->count & 7u) ||
+        ((uintptr_t)b->arena_used & 7u) || ((uintptr_t)b->order & 3u) || ((uintptr_t)b->off64 & 3u) ||
+        ((uintptr_t)b->len & 1u) || ((uintptr_t)b->recs & (rec_align(b->rec_kind) - 1u)))
+        return fail(-EINVAL, "rxg_train_payload_dev: frames and arena need 16-byte, msgs, tmsgs, trains, count and "
+                             "arena_used 8-byte, order and off64 4-byte, len 2-byte, recs %u-byte alignment",
+                    (unsigned)rec_align(b->rec_kind));
+    int rc = check_frame_src("rxg_train_payload_dev", b->off64, b->slot0, b->stride64, b->n);
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchTrainPay L;
+    L.src = FrameSrc{(const uint8_t *)b->frames, b->off64, b->len, b->slot0, b->stride64};
+    L.n = b->n;
+    L.rec_kind = b->rec_kind;
+    L.recs = (const uint8_t *)b->recs;
+    L.order = b->order;
+    L.cap_seg = b->cap_seg;
+    L.trains = b->trains;
+    L.cap_trains = b->cap_trains;
+    L.count = (const unsigned long long *)b->count;
+    L.flags = b->flags;
+    L.arena = (uint8_t *)b->arena;
+    L.arena_cap = b->arena ? b->arena_cap : 0;
+    L.msgs = b->msgs;
+    L.tmsgs = b->tmsgs;
+    L.used = (unsigned long long *)b->arena_used;
+    L.scratch = nullptr;
+    L.max_blocks = grid_cap(c, c->op_grid[kGridTrainPay]);
+    // one gather or train payload in flight per context (rxg_payload_gather_dev's rule): the
+    // messages rxg_payload_take reads are the last such call's
+    if (b->msgs && c->pm_ev) HIP_OK(hipStreamWaitEvent(st, c->pm_ev, 0));
+    if (b->n) {
+        DevBuf &scratch = c->tp.buf[0];
+        if ((rc = c->tp.grow(scratch, train_pay_scratch_bytes(b->n, b->cap_trains), false, st))) return rc;
+        if ((rc = c->tp.begin(st))) return rc;
+        L.scratch = scratch.p;
+    }
+    if ((rc = c->tp.end(st, launch_train_pay(L, st)))) return rc;
+    if (b->msgs) {  // rxg_payload_take fetches the descriptors on its first call after this one
+        if (!c->pm_ev) HIP_OK(hipEventCreateWithFlags(&c->pm_ev, hipEventDisableTiming));
+        HIP_OK(hipEventRecord(c->pm_ev, st));
+        c->d_pm = b->msgs;
+        c->pm_used = b->arena_used;
+        c->pm_n = b->n;
+        c->pm_pending = true;
+        c->pm_poisoned = false;
+    }
+    return 0;
 }

@@ -12,6 +12,7 @@ The reference surface this mirrors (rajneshrat/dpdk-tcpipstack, tcp_ip_stack/):
   (no counterpart: received TCP options)     -> Engine.rx_opts_dev, rx_opt_parse, rx_opts_attach / rx_opt_current
   on_segment's per-flow work (tcp_in.c:66-71) -> Engine.flow_sums_dev, flow_sums_host, flow_sums_attach / flow_sum_current
   PushData on in-order segments (tcp_windows.c:341-358) -> Engine.flow_trains_dev, flow_trains_host, flow_trains_attach / flow_train_current
+  GetData's copy, a train at a time (tcp_windows.c:138-186) -> Engine.train_payload_dev, train_payload_host
 """
 from __future__ import annotations
 
@@ -84,7 +85,7 @@ REC48_DTYPE = np.dtype([("c", REC16_DTYPE), ("ether_type", "<u2"), ("sport", "<u
                         ("seq", "<u4"), ("ack", "<u4"), ("src_ip", "<u4"),
                         ("dst_ip_raw", "<u4"), ("data_off", "u1"), ("src_mac", "u1", (6,)),
                         ("reserved", "u1")])
-PM_GATHERED, PM_REF_OVERSIZE = 0x01, 0x02
+PM_GATHERED, PM_REF_OVERSIZE, PM_HOLE = 0x01, 0x02, 0x04
 PAYLOAD_MSG_DTYPE = np.dtype([("arena_off", "<u8"), ("len", "<u4"), ("flags", "<u4")])
 TCB_DTYPE = np.dtype([("dport", "<i4"), ("sport", "<i4"), ("ipv4_dst", "<u4"),
                       ("ipv4_src", "<u4"), ("state", "u1"), ("pad", "u1"),
@@ -135,6 +136,12 @@ FT_TCP_OK_ONLY = 1
 FLOW_TRAIN_TILE = 1024
 FLOW_TRAIN_ROUND_LANES = 256
 FLOW_TRAIN_SCAN_ROUND = 1024 * 16
+# a burst's payload gathered by train (rxg_train_payload_dev, rxg_train_payload_host)
+TP_HEAD_ONLY = 1
+# csrc/rxg_kernels.h kTpTile / kTpScanLanes: trains per tile of the offsets (and segments per tile
+# of the copy), tile sums per round of the one-workgroup scan: a round covers TILE * SCAN_TILES trains
+TRAIN_PAY_TILE = 256
+TRAIN_PAY_SCAN_TILES = 256
 
 
 
@@ -308,6 +315,15 @@ class DevFlowSums(C.Structure):
                 ("count", C.c_void_p)]
 
 
+class DevTrainPayload(C.Structure):
+    """rxg_dev_train_payload."""
+    _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
+                ("stride64", C.c_uint32), ("n", C.c_uint32), ("rec_kind", C.c_uint32), ("recs", C.c_void_p),
+                ("order", C.c_void_p), ("cap_seg", C.c_uint64), ("trains", C.c_void_p), ("cap_trains", C.c_uint64),
+                ("count", C.c_void_p), ("flags", C.c_uint32), ("arena", C.c_void_p), ("arena_cap", C.c_uint64),
+                ("msgs", C.c_void_p), ("tmsgs", C.c_void_p), ("arena_used", C.c_void_p)]
+
+
 class DevFlowTrains(C.Structure):
     """rxg_dev_flow_trains."""
     _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
@@ -446,6 +462,8 @@ def load_library(path: str = LIB_PATH):
         "rxg_flow_trains_host": (C.c_int, [vp, u32, vp, vp, u32, u32, u32, vp, vp, u64, vp, u64, vp]),
         "rxg_flow_trains_attach": (C.c_int, [vp, vp, u64, vp, u64]),
         "rxg_flow_train_current": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u32)]),
+        "rxg_train_payload_dev": (C.c_int, [vp, C.POINTER(DevTrainPayload), vp]),
+        "rxg_train_payload_host": (C.c_int, [vp, u32, vp, vp, u32, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -762,6 +780,45 @@ def flow_trains_host(recs, rec_kind: int, ntcb: int, frames=None, flags: int = 0
         raise RxgError(f"rxg_flow_trains_host failed ({rc})")
     return (obuf if order is not None else obuf[:min(int(count[0]), cap_seg)].copy(),
             tbuf if trains is not None else tbuf[:min(int(count[1]), cap_trains)].copy(), count)
+
+
+def train_payload_host(recs, rec_kind: int, frames, order, trains, count, flags: int = 0, arena_cap=None, arena=None,
+                       want_msgs: bool = True, want_tmsgs: bool = True):
+    """rxg_train_payload_host: the burst's payload gathered by train, in host memory.  recs /
+    frames as flow_trains_host's (frames required); order, trains, count: what flow_trains_host
+    returned for the burst (cap_seg = len(order), cap_trains = len(trains)).  arena: a uint8 array
+    written in place, or None for a zeroed one of arena_cap bytes (None: what the burst needs).
+    Returns (arena, msgs PAYLOAD_MSG_DTYPE[n] or None, tmsgs PAYLOAD_MSG_DTYPE[len(trains)] or
+    None, arena_used)."""
+    lib = load_library()
+    recs = np.ascontiguousarray(recs)
+    n = recs.nbytes // rec_kind
+    if len(frames) != n:
+        raise ValueError("train_payload_host: one frame per record")
+    keep = [C.create_string_buffer(bytes(f), max(len(f), 1)) for f in frames]
+    ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(b) for b in keep])
+    lens = np.array([len(f) for f in frames], np.uint16)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    trains = np.ascontiguousarray(trains, dtype=FLOW_TRAIN_DTYPE)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if arena is None:
+        if arena_cap is None:
+            arena_cap = int(((trains["bytes"].astype(np.uint64) + np.uint64(15)) & ~np.uint64(15)).sum())
+        arena = np.zeros(arena_cap, np.uint8)
+    elif arena_cap is None:
+        arena_cap = len(arena)
+    msgs = np.zeros(max(n, 1), PAYLOAD_MSG_DTYPE) if want_msgs else None
+    tmsgs = np.zeros(max(len(trains), 1), PAYLOAD_MSG_DTYPE) if want_tmsgs else None
+    used = np.zeros(1, np.uint64)
+    rc = lib.rxg_train_payload_host(_ptr(recs) if n else None, rec_kind, ptrs, _ptr(lens) if n else None, n,
+                                    _ptr(order) if len(order) else None, len(order),
+                                    _ptr(trains) if len(trains) else None, len(trains), _ptr(count), flags,
+                                    _ptr(arena) if len(arena) else None, arena_cap,
+                                    None if msgs is None else _ptr(msgs), None if tmsgs is None else _ptr(tmsgs),
+                                    _ptr(used))
+    if rc:
+        raise RxgError(f"rxg_train_payload_host failed ({rc})")
+    return (arena, None if msgs is None else msgs[:n], None if tmsgs is None else tmsgs[:len(trains)], int(used[0]))
 
 
 # -------------------------------------------------------------------------- engine ---
@@ -1134,6 +1191,19 @@ class Engine:
         b = DevFlowTrains(frames, off64, lens, slot0, stride64, n, rec_kind, recs, ntcb, flags, cur_seq, order, cap_seg,
                           trains, cap_trains, count)
         _check(_lib.rxg_flow_trains_dev(self.ctx, C.byref(b), stream), "rxg_flow_trains_dev")
+
+    def train_payload_dev(self, frames: int, lens: int, n: int, recs: int, rec_kind: int, order: int | None,
+                          cap_seg: int, trains: int | None, cap_trains: int, count: int, arena: int | None,
+                          arena_cap: int, msgs: int | None, tmsgs: int | None, arena_used: int,
+                          off64: int | None = None, slot0: int = 0, stride64: int = 0, flags: int = 0, stream=None):
+        """rxg_train_payload_dev: the burst's payload gathered by train into arena (each taking
+        train's bytes contiguous, 16-byte aligned, pads zero), one PAYLOAD_MSG_DTYPE per frame at
+        msgs + 16 * i and per train at tmsgs + 16 * k, the bytes needed at arena_used.  order,
+        trains, count: a flow_trains_dev call's outputs for the burst.  All device addresses.  With
+        msgs the burst is registered for payload_take as after payload_gather_dev."""
+        b = DevTrainPayload(frames, off64, lens, slot0, stride64, n, rec_kind, recs, order, cap_seg, trains, cap_trains,
+                            count, flags, arena, arena_cap, msgs, tmsgs, arena_used)
+        _check(_lib.rxg_train_payload_dev(self.ctx, C.byref(b), stream), "rxg_train_payload_dev")
 
     def flow_trains_attach(self, order_host: int, nseg: int, trains_host: int, ntrains: int):
         """rxg_flow_trains_attach: host copies (addresses) of a flow_trains_dev call's order and trains

@@ -1154,6 +1154,112 @@ int rxg_flow_trains_attach(rxg_ctx *ctx, const uint32_t *order_host, uint64_t ns
 int rxg_flow_train_current(rxg_ctx *ctx, const rxg_flow_train **out, uint32_t *pos);
 
 /* ------------------------------------------------------------------------- */
+/* A burst's payload gathered by train: each train's bytes contiguous in the   */
+/* arena, in sequence order, with one message per segment (what                */
+/* rxg_payload_take answers from) and one per train (what a stream reader      */
+/* takes whole).  The inputs are a burst and the outputs of                    */
+/* rxg_flow_trains_dev / rxg_flow_trains_host on it: order, trains, count.     */
+/*                                                                             */
+/* Which trains take part.  S' = min(count[0], cap_seg, n), T' = min(count[1], */
+/* cap_trains, n) (a burst of n frames has no more segments or trains than n); */
+/* with S' == 0, T' is taken as 0.  Train k < T' takes part when               */
+/* its segments lie whole inside order[0, S'): (uint64_t)first + nseg <= S'    */
+/* (and bytes < 2^32, as every train the flow-train call writes has); with     */
+/* RXG_TP_HEAD_ONLY it must also carry RXG_FTR_HEAD.  A WRAP train takes part  */
+/* like any other (rxg_payload_take refuses its segment at replay time).       */
+/*                                                                             */
+/* Placement.  The taking trains are placed in train order: train k's span     */
+/* starts at train_off = the sum of (bytes + 15) & ~15 over the taking trains  */
+/* before it, so every span starts 16-byte aligned.  *arena_used is that sum   */
+/* over all taking trains, whatever arena_cap is.  A taking train is placed    */
+/* when train_off + ((bytes + 15) & ~15) <= arena_cap; the trains that are not */
+/* are a suffix of the taking trains, and nothing of them is gathered.         */
+/*                                                                             */
+/* Bytes.  Segment j of a placed train (packet i = order[first + j]) is a      */
+/* candidate when i < n, its record's verdict is DISPATCH, RST_NOPCB or        */
+/* RST_LISTEN_NONSYN, datalen > 0, RXG_F_TRUNC is clear, len[i] > 46, and with */
+/* start = 34 + (frame[46] >> 4) * 4 (GetData's address, tcp_windows.c:164-166:*/
+/* the IP header taken as 20 bytes) start + datalen <= len[i]: the rule of     */
+/* rxg_payload_gather_dev.  Its place is rel = (uint32_t)(seq_i - seq_train),  */
+/* seq_i read as rxg_flow_trains_dev reads it; a candidate must also lie       */
+/* inside its train, rel + datalen <= bytes (always so for the trains the      */
+/* flow-train call wrote for this burst).  A candidate's datalen payload bytes */
+/* frame[start ..) are written at arena + train_off + rel.  A segment that is  */
+/* no candidate is a hole: its bytes in the span are left untouched and its    */
+/* train's message carries RXG_PM_HOLE.  The pad bytes of a placed train,      */
+/* [train_off + bytes, train_off + ((bytes + 15) & ~15)), are written as zero. */
+/* No other byte of the arena is written.                                      */
+/*                                                                             */
+/* msgs[i], one per FRAME of the burst (may be NULL): for a copied segment     */
+/* {train_off + rel, datalen, RXG_PM_GATHERED | RXG_PM_REF_OVERSIZE where      */
+/* datalen >= 1000}; arena_off is not 16-byte aligned.  Every other frame's    */
+/* message is all zero.  tmsgs[k], one per TRAIN k < T' (may be NULL): for a   */
+/* placed train {train_off, (uint32_t)bytes, RXG_PM_GATHERED | RXG_PM_HOLE if  */
+/* it has a hole}; for a train that does not take part or is not placed, all   */
+/* zero.  tmsgs[k] for k >= T' is not written.                                 */
+/*                                                                             */
+/* n == 0: *arena_used = 0 and nothing else.  S' == 0: *arena_used = 0, msgs   */
+/* (if given) all zero, nothing else.  The output is a pure function of the    */
+/* arguments: never of the grid, the stream or an earlier call.                */
+/* ------------------------------------------------------------------------- */
+#define RXG_TP_HEAD_ONLY 0x1u  /* only trains that carry RXG_FTR_HEAD take part */
+
+struct rxg_payload_msg;        /* (defined with the payload hand-off below) */
+
+/* frames / off64 / len / slot0 / stride64 / recs / rec_kind name the burst as rxg_dev_flow_trains
+   does, but frames and len are required for every record kind (the payload is read from the
+   frame).  Asynchronous on `stream`: msgs zeroed, then four launches -- the taking trains' padded
+   sizes summed per tile of 256 trains, a one-workgroup scan of the tile sums (which writes
+   *arena_used), the trains' offsets and tmsgs, and the copy: a workgroup per tile of 256
+   consecutive entries of `order` finds its first segment's train by a search over
+   trains[].first, the other segments' by marking the train starts inside the tile, and shares
+   the tile's 16-byte destination chunks out over its lanes.  Nothing waits on another workgroup,
+   no atomic decides a position (RXG_PM_HOLE is ORed into a train's flags), count is read on the
+   device only, and rxg_config.max_blocks caps the grids.  Payloads are read with 16-byte loads
+   inside the 64-byte slots a frame's len occupies.  The context owns the scratch (8 bytes per
+   train), grown on demand; one call at a time uses it, as for rxg_flow_trains_dev.
+   When msgs is not NULL the call registers the burst for rxg_payload_take exactly as
+   rxg_payload_gather_dev does (msgs and arena_used must stay valid until the burst's replay is
+   done; one such call or gather is in flight per context); arena_used is never UINT64_MAX.
+   -EINVAL: a NULL ctx, p, frames, len, recs, order (cap_seg != 0), trains (cap_trains != 0),
+   count, arena_used, or arena with arena_cap != 0; a bad rec_kind; unknown flag bits; frames or
+   arena not 16-, msgs, tmsgs, trains, count or arena_used not 8-, order or off64 not 4-, len
+   not 2-byte aligned, recs not 8- (RXG_REC8) or 16-byte aligned; stride64 0 or slot0 + (n - 1) *
+   stride64 over 2^32 - 1 in strided mode.  -ENOMEM: the scratch cannot be allocated; nothing is
+   launched then. */
+typedef struct rxg_dev_train_payload {
+    const void *frames;       /* dev: the burst's frame pool                                     */
+    const uint32_t *off64;    /* dev, n entries; NULL = fixed stride (slot0 + i * stride64)      */
+    const uint16_t *len;      /* dev, n entries                                                  */
+    uint32_t slot0, stride64; /* used when off64 == NULL                                         */
+    uint32_t n;
+    uint32_t rec_kind;        /* RXG_REC8 / RXG_REC16 / RXG_REC48                                */
+    const void *recs;         /* dev: the burst's n records                                      */
+    const uint32_t *order;    /* dev: rxg_flow_trains_dev's order for this burst, cap_seg entries */
+    uint64_t cap_seg;
+    const rxg_flow_train *trains; /* dev: its trains, cap_trains entries                         */
+    uint64_t cap_trains;
+    const uint64_t *count;    /* dev: its 4 count words, read on the device                      */
+    uint32_t flags;           /* RXG_TP_*                                                        */
+    void *arena;             /* dev, 16-byte aligned, arena_cap bytes                           */
+    uint64_t arena_cap;
+    struct rxg_payload_msg *msgs;   /* dev, n entries, one per FRAME; may be NULL                */
+    struct rxg_payload_msg *tmsgs;  /* dev, cap_trains entries, one per TRAIN; may be NULL       */
+    uint64_t *arena_used;     /* dev, 1 word, WRITTEN                                            */
+} rxg_dev_train_payload;
+int rxg_train_payload_dev(rxg_ctx *ctx, const rxg_dev_train_payload *p, void *stream);
+
+/* Host form of the rule (no context, no GPU): frame i is frames[i][0 .. len[i]); order, trains
+   and count as rxg_flow_trains_host wrote them.  Returns 0; -EINVAL: count or arena_used NULL,
+   recs, frames or len NULL with n != 0, order NULL with cap_seg != 0, trains NULL with
+   cap_trains != 0, arena NULL with arena_cap != 0, a bad rec_kind, unknown flag bits. */
+int rxg_train_payload_host(const void *recs, uint32_t rec_kind, void *const *frames, const uint16_t *len,
+                           uint32_t n, const uint32_t *order, uint64_t cap_seg, const rxg_flow_train *trains,
+                           uint64_t cap_trains, const uint64_t count[4], uint32_t flags, void *arena,
+                           uint64_t arena_cap, struct rxg_payload_msg *msgs, struct rxg_payload_msg *tmsgs,
+                           uint64_t *arena_used);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
@@ -1249,13 +1355,17 @@ int rxg_ether_in(rxg_ctx *ctx, const rxg_handoff_ops *ops, void *mbuf, void *fra
 /* ------------------------------------------------------------------------- */
 enum rxg_payload_flag {
     RXG_PM_GATHERED = 0x01,     /* arena holds this frame's payload                          */
-    RXG_PM_REF_OVERSIZE = 0x02  /* len >= 1000: the reference's GetData asserts here
+    RXG_PM_REF_OVERSIZE = 0x02, /* len >= 1000: the reference's GetData asserts here
                                    (tcp_windows.c:170, its Buffer[1000]); rxg delivers it   */
+    RXG_PM_HOLE = 0x04          /* a train's message (rxg_train_payload_dev tmsgs): a segment
+                                   of the train was not copied, its bytes are not in the span */
 };
 
 typedef struct rxg_payload_msg {
     uint64_t arena_off;  /* payload at arena + arena_off: 16-byte aligned (gather), or the
-                            payload's offset in the frame pool (rxg_rx_burst_payload_dev)   */
+                            payload's offset in the frame pool (rxg_rx_burst_payload_dev), or
+                            its place inside its train's span (rxg_train_payload_dev: any
+                            alignment; a train's own message is 16-byte aligned)            */
     uint32_t len;        /* Length = datalen (tcp_states.c:111), bytes at frame + 34 +
                             (data_off >> 4) * 4 (tcp_windows.c:164-166); 0 if not gathered   */
     uint32_t flags;      /* RXG_PM_*                                                        */
