@@ -4,7 +4,7 @@
 //                   HipTablePort, the device side of rxg_tablesync.h
 //   rxg_ops.cpp     the operations on a burst beside its classification: tx checksums, segment
 //                   build, reset build, transmit planner, received options, flow summary,
-//                   flow trains, train payload
+//                   flow trains, train payload, ACK plan
 //   rxg_tablesync.h the device tables and the order of their writes against the kernels that
 //                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "rxg.h"
@@ -142,7 +143,7 @@ struct SerialScratch {
 
 // The operations whose launch grid the context works out once, at init (rxg_ctx::op_grid).
 enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridFlowTrain,
-              kGridTrainPay, kGridOps };
+              kGridTrainPay, kGridAckPlan, kGridOps };
 
 struct rxg_ctx {
     int device = 0;
@@ -260,6 +261,20 @@ struct rxg_ctx {
     uint64_t ft_nseg = 0, ft_ntrains = 0;
     // rxg_train_payload_dev: the trains' offsets and the tile sums (buf[0]); no content is kept
     SerialScratch tp{"rxg_train_payload_dev"};
+    // rxg_ack_plan_dev: the tile sums (buf[0]); no content is kept
+    SerialScratch ak{"rxg_ack_plan_dev"};
+    // rxg_acks_attach: host copies of a call's acks and of the frames built from its segs.  ak_phase
+    // 1: attached, waiting for its replay; 2: that replay has begun (rxg_ack_take answers, also
+    // after it returned); the next replay, attach or fini ends it.  What the replay saw that voids
+    // a prebuilt ACK: the TCBs a re-classification took a packet from or gave one to, the tuples
+    // of written slots (the replay's own write log), a whole-table change
+    const rxg_ack *ak_acks = nullptr;
+    uint8_t *ak_frames = nullptr;
+    uint64_t ak_n = 0;
+    uint32_t ak_stride = 0, ak_phase = 0;
+    std::unordered_set<int32_t> ak_void_tcb;
+    std::unordered_set<rxg::TupleKey, rxg::TupleKeyHash> ak_void_keys;
+    bool ak_void_all = false;
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;

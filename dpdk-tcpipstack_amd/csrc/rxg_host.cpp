@@ -98,6 +98,8 @@ extern "C" int rxg_init(const rxg_config *cfg, rxg_ctx **out)
         c->op_grid[kGridFlowTrain] = cus * (uint32_t)flow_train_blocks_per_cu();
         // rxg_train_payload_dev: the occupancy grid of its copy
         c->op_grid[kGridTrainPay] = cus * (uint32_t)train_pay_blocks_per_cu();
+        // rxg_ack_plan_dev: the occupancy grid of its emit pass
+        c->op_grid[kGridAckPlan] = cus * (uint32_t)ack_plan_blocks_per_cu();
     }
     // a large BAR: the mirror's patch lists live in device memory the host writes directly,
     // and a burst launch carries its own (launch_bursts)
@@ -178,7 +180,7 @@ extern "C" int rxg_fini(rxg_ctx *c)
     for (DevBuf *b : {&c->tables.buckets, &c->tables.listen, &c->d_sel, &c->d_fix, &c->tables.d_arp, &c->d_pg_status,
                       &c->d_pg_ticket, &c->d_soff})
         if (b->p) (void)hipFree(b->p);
-    for (SerialScratch *s : {&c->rst, &c->txp, &c->fs, &c->ft, &c->tp}) s->destroy();
+    for (SerialScratch *s : {&c->rst, &c->txp, &c->fs, &c->ft, &c->tp, &c->ak}) s->destroy();
     if (c->h_pm) (void)hipHostFree(c->h_pm);
     if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
     c->tables.destroy();

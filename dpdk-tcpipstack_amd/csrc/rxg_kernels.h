@@ -328,6 +328,32 @@ struct LaunchTrainPay {
 hipError_t launch_train_pay(const LaunchTrainPay &P, hipStream_t st);
 size_t train_pay_scratch_bytes(uint32_t n, unsigned long long cap_trains);
 int train_pay_blocks_per_cu();  // resident 256-thread workgroups per CU of the copy
+// rxg_ackplan.hip: a burst's ACKs planned per flow (rxg_ack_plan_dev): the flows' classes summed per
+// tile, their one-workgroup scan and the descriptors, records and option blocks on `st` (no
+// train readable -- n, cap_seg or cap_trains 0: count = {0, 0, 0, 0} only)
+constexpr uint32_t kAkTile = 256;        // trains per tile
+constexpr uint32_t kAkScanLanes = 256;   // tile sums per round of the one-workgroup scan
+struct LaunchAckPlan {
+    const uint32_t *order;
+    unsigned long long cap_seg;
+    const rxg_flow_train *trains;
+    unsigned long long cap_trains;
+    const unsigned long long *train_count;  // the flow-train call's 4 words, read on the device
+    uint32_t n, ntcb;
+    const rxg_rx_opt *rxopts;         // may be nullptr
+    const rxg_ack_state *state;
+    uint32_t tsval_now, ip_id0, opt_plain, opt_base, opt_cap;
+    rxg_tx_opt *opts;                 // may be nullptr
+    rxg_tx_seg *segs;
+    rxg_ack *acks;
+    unsigned long long cap;
+    unsigned long long *count;        // 4 words
+    void *scratch;                    // ack_plan_scratch_bytes(n, cap_trains) bytes, any content
+    uint32_t max_blocks;              // grid cap of the count and emit passes; 0 = 2^16
+};
+hipError_t launch_ack_plan(const LaunchAckPlan &P, hipStream_t st);
+size_t ack_plan_scratch_bytes(uint32_t n, unsigned long long cap_trains);
+int ack_plan_blocks_per_cu();  // resident 256-thread workgroups per CU of the emit pass
 // resident 256-thread workgroups per CU of the production kernel of `mode` (by_ref: the
 // by-reference payload hand-off's, whose record ring also stages the messages)
 int rx_blocks_per_cu(int mode, bool by_ref = false);

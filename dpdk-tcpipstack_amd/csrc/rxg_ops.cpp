@@ -1,6 +1,7 @@
 // rxg_ops.cpp — the operations on a burst beside its classification (include/rxg.h): tx
 // checksums, segment build with and without options, reset build, transmit planner,
-// received-option parse, flow summary, flow trains, train payload.  Each entry point checks its arguments,
+// received-option parse, flow summary, flow trains, train payload, ACK plan.  Each entry point checks its
+// arguments,
 // fills its kernels' launch struct (rxg_kernels.h) and launches on the caller's stream; what
 // they share -- rec_align, check_frame_src, grid_cap, SerialScratch -- is in rxg_ctx.h.
 #include <cstring>
@@ -359,4 +360,58 @@ extern "C" int rxg_train_payload_dev(rxg_ctx *c, const rxg_dev_train_payload *b,
         c->pm_poisoned = false;
     }
     return 0;
+}
+
+static_assert(sizeof(rxg_ack_state) == 16 && sizeof(rxg_ack) == 16 && sizeof(rxg_dev_ack_plan) == 128,
+              "ACK plan layouts");
+
+extern "C" int rxg_ack_plan_dev(rxg_ctx *c, const rxg_dev_ack_plan *b, void *stream)
+{
+    if (!c || !b) return fail(-EINVAL, "rxg_ack_plan_dev: NULL argument");
+    if (!b->train_count || !b->state || !b->count || (!b->order && b->cap_seg) || (!b->trains && b->cap_trains) ||
+        ((!b->segs || !b->acks) && b->cap))
+        return fail(-EINVAL, "rxg_ack_plan_dev: NULL device pointer");
+    if (b->ntcb == 0 || b->ntcb > RXG_FS_MAX_NTCB) return fail(-EINVAL, "rxg_ack_plan_dev: ntcb %u", b->ntcb);
+    if (b->flags) return fail(-EINVAL, "rxg_ack_plan_dev: unknown flags 0x%x", b->flags);
+    if (b->opt_plain > b->opt_base || b->opt_base > b->opt_cap)
+        return fail(-EINVAL, "rxg_ack_plan_dev: opt_plain %u, opt_base %u, opt_cap %u", b->opt_plain, b->opt_base,
+                    b->opt_cap);
+    if (((uintptr_t)b->state & 15u) || ((uintptr_t)b->rxopts & 15u) || ((uintptr_t)b->opts & 15u) ||
+        ((uintptr_t)b->segs & 15u) || ((uintptr_t)b->acks & 15u) || ((uintptr_t)b->trains & 7u) ||
+        ((uintptr_t)b->train_count & 7u) || ((uintptr_t)b->count & 7u) || ((uintptr_t)b->order & 3u))
+        return fail(-EINVAL, "rxg_ack_plan_dev: state, rxopts, opts, segs and acks need 16-byte, trains, train_count "
+                             "and count 8-byte, order 4-byte alignment");
+    int rc = set_device(c);
+    if (rc) return rc;
+    hipStream_t st = pick(c, stream);
+    LaunchAckPlan L;
+    L.order = b->order;
+    L.cap_seg = b->order ? b->cap_seg : 0;
+    L.trains = b->trains;
+    L.cap_trains = b->trains ? b->cap_trains : 0;
+    L.train_count = (const unsigned long long *)b->train_count;
+    L.n = b->n;
+    L.ntcb = b->ntcb;
+    L.rxopts = b->rxopts;
+    L.state = b->state;
+    L.tsval_now = b->tsval_now;
+    L.ip_id0 = b->ip_id0;
+    L.opt_plain = b->opt_plain;
+    L.opt_base = b->opt_base;
+    L.opt_cap = b->opt_cap;
+    L.opts = b->opts;
+    L.segs = b->segs;
+    L.acks = b->acks;
+    L.cap = b->cap;
+    L.count = (unsigned long long *)b->count;
+    L.scratch = nullptr;
+    L.max_blocks = grid_cap(c, c->op_grid[kGridAckPlan]);
+    const size_t bytes = ack_plan_scratch_bytes(b->n, L.cap_trains);
+    if (bytes) {
+        DevBuf &scratch = c->ak.buf[0];
+        if ((rc = c->ak.grow(scratch, bytes, false, st))) return rc;
+        if ((rc = c->ak.begin(st))) return rc;
+        L.scratch = scratch.p;
+    }
+    return c->ak.end(st, launch_ack_plan(L, st));
 }

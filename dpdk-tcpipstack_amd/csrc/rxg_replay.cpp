@@ -2,8 +2,8 @@
 // (rxg_rx_replay: the reference's ether_in -> ip_in -> tcp_in order, re-classifying what a
 // handler's table write changed), the payload hand-off (rxg_payload_gather_dev, rxg_rcv_set,
 // rxg_payload_take), the prebuilt resets' hand-out (rxg_reset_attach, rxg_reset_take), the
-// parsed options' (rxg_rx_opts_attach, rxg_rx_opt_current) and the
-// one-frame rxg_ether_in.
+// parsed options' (rxg_rx_opts_attach, rxg_rx_opt_current), the prebuilt ACKs' (rxg_acks_attach,
+// rxg_ack_take) and the one-frame rxg_ether_in.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -277,6 +277,56 @@ extern "C" int rxg_flow_train_current(rxg_ctx *c, const rxg_flow_train **out, ui
     return 1;
 }
 
+// ------------------------------------------------------------------ prebuilt ACKs ---
+static void acks_detach(rxg_ctx *c)
+{
+    c->ak_acks = nullptr;
+    c->ak_frames = nullptr;
+    c->ak_n = 0;
+    c->ak_stride = c->ak_phase = 0;
+    c->ak_void_tcb.clear();
+    c->ak_void_keys.clear();
+    c->ak_void_all = false;
+}
+
+extern "C" int rxg_acks_attach(rxg_ctx *c, const rxg_ack *acks_host, void *frames_host, uint32_t stride, uint64_t nacks)
+{
+    if (!c || (nacks && (!acks_host || !frames_host || !stride)))
+        return fail(-EINVAL, "rxg_acks_attach: NULL argument or stride 0");
+    for (uint64_t a = 1; a < nacks; ++a)
+        if (acks_host[a].tcb_idx <= acks_host[a - 1].tcb_idx)
+            return fail(-EINVAL, "rxg_acks_attach: entry %llu is not above its predecessor's tcb_idx",
+                        (unsigned long long)a);
+    acks_detach(c);
+    if (!nacks) return 0;
+    c->ak_acks = acks_host;
+    c->ak_frames = (uint8_t *)frames_host;
+    c->ak_stride = stride;
+    c->ak_n = nacks;
+    c->ak_phase = 1;
+    return 0;
+}
+
+// The attached ACK of tcb_idx, if it still says what the stack's state says and nothing voids
+// it: no packet re-classified to or from the TCB, no write to its slot (the slot's tuple is among
+// the written ones, or the slot is gone), no whole-table change -- in the replay, or since it
+// returned (the writes not yet absorbed: touched_keys / touched_all, kept until the next burst).
+extern "C" int rxg_ack_take(rxg_ctx *c, int32_t tcb_idx, uint32_t snd_nxt, uint32_t rcv_ack, void **frame_out)
+{
+    if (!c || !frame_out) return fail(-EINVAL, "rxg_ack_take: NULL argument");
+    if (c->ak_phase != 2u || c->ak_void_all) return 0;
+    const rxg_ack *lo = c->ak_acks, *hi = c->ak_acks + c->ak_n;
+    const rxg_ack *e = std::lower_bound(lo, hi, tcb_idx, [](const rxg_ack &x, int32_t t) { return x.tcb_idx < t; });
+    if (e == hi || e->tcb_idx != tcb_idx || e->seq != snd_nxt || e->ack != rcv_ack) return 0;
+    if (tcb_idx < 0 || tcb_idx >= c->mir.ntcb() || !c->mir.live[tcb_idx]) return 0;
+    TupleKey k;
+    if (!tcb_key(c->mir.tcb[tcb_idx], k)) return 0;
+    if (c->ak_void_tcb.count(tcb_idx) || c->ak_void_keys.count(k)) return 0;
+    if (c->touched_all || std::find(c->touched_keys.begin(), c->touched_keys.end(), k) != c->touched_keys.end()) return 0;
+    *frame_out = c->ak_frames + (size_t)(e - lo) * c->ak_stride;
+    return 1;
+}
+
 // ------------------------------------------------------------------------- replay ---
 static inline bool rec_is_tcp(const rxg_rec16 &r)
 {
@@ -383,8 +433,12 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
     // (rxg_reset_attach) are no longer named
     struct PosGuard {
         rxg_ctx *c;
+        bool done = false;  // the replay ran to its end
         ~PosGuard()
         {
+            // prebuilt ACKs (rxg_acks_attach) are only handed out after a replay that saw the whole
+            // burst: one that fails, in its argument checks or later, ends the attachment
+            if (!done) acks_detach(c);
             c->replay_pos = -1;
             c->rst_host = nullptr;
             c->rst_idx = nullptr;
@@ -399,6 +453,11 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
             c->ft_nseg = c->ft_ntrains = 0;
         }
     } pos_guard{c};
+    // the prebuilt ACKs (rxg_acks_attach) outlive one replay: an attachment that has had its
+    // replay ends here, a fresh one belongs to this burst (and ends with it if it fails: pos_guard)
+    if (c->ak_phase == 2u) acks_detach(c);
+    else if (c->ak_phase == 1u) c->ak_phase = 2u;
+    const bool ak_on = c->ak_phase == 2u;
     if (!ops || (n && (!mbufs || !frames || !recs)))
         return fail(-EINVAL, "rxg_rx_replay: NULL argument");
     if (!rec_kind_ok(stride)) return fail(-EINVAL, "rxg_rx_replay: stride %u", stride);
@@ -436,6 +495,10 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
                             bool pass2) {
         ++wseq;
         any_seq = wseq;
+        if (ak_on) {  // what voids a prebuilt ACK (rxg_ack_take)
+            c->ak_void_all |= all;
+            c->ak_void_keys.insert(keys.begin(), keys.end());
+        }
         if (all) all_seq = bulk_seq = wseq;
         if (pass2) minnull_seq = bulk_seq = wseq;
         for (const TupleKey &k : keys) {
@@ -517,6 +580,10 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
                     for (size_t k = 0; k < sel.size(); ++k) {
                         tcp_record_counters(cur[sel[k]], -1, delta);
                         tcp_record_counters(fix[k], +1, delta);
+                        if (ak_on) {
+                            c->ak_void_tcb.insert(cur[sel[k]].tcb_idx);
+                            c->ak_void_tcb.insert(fix[k].tcb_idx);
+                        }
                         cur[sel[k]] = fix[k];
                         pkt_seq[sel[k]] = wseq;
                     }
@@ -534,6 +601,10 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
                 host_classify(c, (const uint8_t *)frames[i], r);
                 tcp_record_counters(cur[i], -1, delta);
                 tcp_record_counters(r, +1, delta);
+                if (ak_on) {
+                    c->ak_void_tcb.insert(cur[i].tcb_idx);
+                    c->ak_void_tcb.insert(r.tcb_idx);
+                }
                 cur[i] = r;
                 pkt_seq[i] = wseq;
                 ++c->rp_stats[1];
@@ -594,6 +665,7 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
         for (int k = 0; k < RXG_NCOUNTERS; ++k) c->pend_delta[k] += delta[k];
         c->pend = true;
     }
+    pos_guard.done = true;
     return 0;
 }
 

@@ -13,6 +13,7 @@ The reference surface this mirrors (rajneshrat/dpdk-tcpipstack, tcp_ip_stack/):
   on_segment's per-flow work (tcp_in.c:66-71) -> Engine.flow_sums_dev, flow_sums_host, flow_sums_attach / flow_sum_current
   PushData on in-order segments (tcp_windows.c:341-358) -> Engine.flow_trains_dev, flow_trains_host, flow_trains_attach / flow_train_current
   GetData's copy, a train at a time (tcp_windows.c:138-186) -> Engine.train_payload_dev, train_payload_host
+  the poll's one ACK per connection (socket_interface.c:214-218) -> Engine.ack_plan_dev, ack_plan_host, acks_attach / ack_take
 """
 from __future__ import annotations
 
@@ -142,6 +143,17 @@ TP_HEAD_ONLY = 1
 # of the copy), tile sums per round of the one-workgroup scan: a round covers TILE * SCAN_TILES trains
 TRAIN_PAY_TILE = 256
 TRAIN_PAY_SCAN_TILES = 256
+# a burst's ACKs planned per flow (rxg_ack_plan_dev, rxg_ack_plan_host): rxg_ack_state, rxg_ack and
+# their RXG_AS_* / RXG_ACK_* flags
+ACK_STATE_DTYPE = np.dtype([("snd_nxt", "<u4"), ("rcv_ack", "<u4"), ("ts_recent", "<u4"), ("win_raw", "<u2"),
+                            ("flags", "<u2")])
+ACK_DTYPE = np.dtype([("tcb_idx", "<i4"), ("ack", "<u4"), ("seq", "<u4"), ("flags_train", "<u4")])
+assert ACK_STATE_DTYPE.itemsize == 16 and ACK_DTYPE.itemsize == 16
+AS_LIVE, AS_TS = 0x1, 0x2
+ACK_ADVANCES, ACK_DUP, ACK_FIN, ACK_NO_OPT = 0x01, 0x02, 0x04, 0x08
+# csrc/rxg_kernels.h kAkTile / kAkScanLanes: trains per tile, tile sums per round of the scan
+ACK_PLAN_TILE = 256
+ACK_PLAN_SCAN_TILES = 256
 
 
 
@@ -324,6 +336,19 @@ class DevTrainPayload(C.Structure):
                 ("msgs", C.c_void_p), ("tmsgs", C.c_void_p), ("arena_used", C.c_void_p)]
 
 
+class DevAckPlan(C.Structure):
+    """rxg_dev_ack_plan (device addresses for rxg_ack_plan_dev, host addresses for rxg_ack_plan_host)."""
+    _fields_ = [("order", C.c_void_p), ("cap_seg", C.c_uint64), ("trains", C.c_void_p), ("cap_trains", C.c_uint64),
+                ("train_count", C.c_void_p), ("n", C.c_uint32), ("ntcb", C.c_uint32), ("rxopts", C.c_void_p),
+                ("state", C.c_void_p), ("flags", C.c_uint32), ("tsval_now", C.c_uint32), ("ip_id0", C.c_uint16),
+                ("pad0", C.c_uint16), ("opt_plain", C.c_uint32), ("opt_base", C.c_uint32), ("opt_cap", C.c_uint32),
+                ("opts", C.c_void_p), ("segs", C.c_void_p), ("acks", C.c_void_p), ("cap", C.c_uint64),
+                ("count", C.c_void_p)]
+
+
+assert C.sizeof(DevAckPlan) == 128
+
+
 class DevFlowTrains(C.Structure):
     """rxg_dev_flow_trains."""
     _fields_ = [("frames", C.c_void_p), ("off64", C.c_void_p), ("len", C.c_void_p), ("slot0", C.c_uint32),
@@ -464,6 +489,10 @@ def load_library(path: str = LIB_PATH):
         "rxg_flow_train_current": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u32)]),
         "rxg_train_payload_dev": (C.c_int, [vp, C.POINTER(DevTrainPayload), vp]),
         "rxg_train_payload_host": (C.c_int, [vp, u32, vp, vp, u32, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp]),
+        "rxg_ack_plan_dev": (C.c_int, [vp, C.POINTER(DevAckPlan), vp]),
+        "rxg_ack_plan_host": (C.c_int, [C.POINTER(DevAckPlan)]),
+        "rxg_acks_attach": (C.c_int, [vp, vp, vp, u32, u64]),
+        "rxg_ack_take": (C.c_int, [vp, i32, u32, u32, C.POINTER(vp)]),
         "rxg_server_start": (C.c_int, [vp, C.POINTER(ServerConfig)]),
         "rxg_server_placement": (C.c_int, [vp]),
         "rxg_server_stop": (C.c_int, [vp]),
@@ -822,6 +851,43 @@ def train_payload_host(recs, rec_kind: int, frames, order, trains, count, flags:
 
 
 # -------------------------------------------------------------------------- engine ---
+def ack_plan_host(order, trains, train_count, n: int, ntcb: int, state, rxopts=None, tsval_now: int = 0,
+                  ip_id0: int = 0, opt_plain: int = 0, opt_base: int = 0, opt_cap: int = 0, opts=None, cap=None,
+                  segs=None, acks=None, flags: int = 0, cap_seg=None, cap_trains=None):
+    """rxg_ack_plan_host: a burst's ACKs planned per flow, in host memory.  order (u32), trains
+    (FLOW_TRAIN_DTYPE), train_count (u64[4]): a flow-trains call's outputs; state (ACK_STATE_DTYPE,
+    ntcb entries); rxopts (RX_OPT_DTYPE, n records) or None; opts (TX_OPT_DTYPE, opt_cap blocks,
+    written in place past opt_base) or None.  segs / acks: arrays of cap entries written in place
+    (default: fresh ones of cap = len(trains)).  Returns (segs, acks, count u64[4]); the entries
+    written are the first min(count[0], cap)."""
+    lib = load_library()
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    trains = np.ascontiguousarray(trains, dtype=FLOW_TRAIN_DTYPE)
+    train_count = np.ascontiguousarray(train_count, dtype=np.uint64)
+    state = np.ascontiguousarray(state, dtype=ACK_STATE_DTYPE)
+    if rxopts is not None:
+        rxopts = np.ascontiguousarray(rxopts, dtype=RX_OPT_DTYPE)
+    if opts is not None and (opts.dtype != TX_OPT_DTYPE or not opts.flags.c_contiguous or len(opts) < opt_cap):
+        raise ValueError("ack_plan_host: opts must be a contiguous TX_OPT_DTYPE array of opt_cap blocks")
+    cap_seg = len(order) if cap_seg is None else cap_seg
+    cap_trains = len(trains) if cap_trains is None else cap_trains
+    cap = len(trains) if cap is None else cap
+    segs = np.zeros(cap, dtype=TX_SEG_DTYPE) if segs is None else segs
+    acks = np.zeros(cap, dtype=ACK_DTYPE) if acks is None else acks
+    if len(segs) < cap or len(acks) < cap or len(state) < ntcb or len(train_count) < 4:
+        raise ValueError("ack_plan_host: an array is shorter than its count")
+    count = np.zeros(4, dtype=np.uint64)
+    b = DevAckPlan(_ptr(order) if len(order) else None, cap_seg, _ptr(trains) if len(trains) else None, cap_trains,
+                   _ptr(train_count), n, ntcb, _ptr(rxopts) if rxopts is not None and len(rxopts) else None,
+                   _ptr(state) if len(state) else None, flags, tsval_now, ip_id0, 0, opt_plain, opt_base, opt_cap,
+                   _ptr(opts) if opts is not None and len(opts) else None, _ptr(segs) if len(segs) else None,
+                   _ptr(acks) if len(acks) else None, cap, _ptr(count))
+    rc = lib.rxg_ack_plan_host(C.byref(b))
+    if rc:
+        raise RxgError(f"rxg_ack_plan_host failed ({rc})")
+    return segs, acks, count
+
+
 class DevArray:
     """A device allocation owned by an Engine."""
 
@@ -1204,6 +1270,34 @@ class Engine:
         b = DevTrainPayload(frames, off64, lens, slot0, stride64, n, rec_kind, recs, order, cap_seg, trains, cap_trains,
                             count, flags, arena, arena_cap, msgs, tmsgs, arena_used)
         _check(_lib.rxg_train_payload_dev(self.ctx, C.byref(b), stream), "rxg_train_payload_dev")
+
+    def ack_plan_dev(self, order: int | None, cap_seg: int, trains: int | None, cap_trains: int, train_count: int,
+                     n: int, ntcb: int, state: int, segs: int | None, acks: int | None, cap: int, count: int,
+                     rxopts: int | None = None, tsval_now: int = 0, ip_id0: int = 0, opt_plain: int = 0,
+                     opt_base: int = 0, opt_cap: int = 0, opts: int | None = None, flags: int = 0, stream=None):
+        """rxg_ack_plan_dev: one ACK descriptor (TX_SEG_DTYPE at segs + 32 * a), one ACK_DTYPE record
+        (acks + 16 * a) and, for timestamp flows, one option block (opts + 48 * (opt_base + a)) per
+        flow of the burst that received data, four u64 at count.  order, trains, train_count: a
+        flow_trains_dev call's outputs; state: ntcb ACK_STATE_DTYPE entries; rxopts: an
+        rx_opts_dev call's records or None.  All device addresses."""
+        b = DevAckPlan(order, cap_seg, trains, cap_trains, train_count, n, ntcb, rxopts, state, flags, tsval_now,
+                       ip_id0, 0, opt_plain, opt_base, opt_cap, opts, segs, acks, cap, count)
+        _check(_lib.rxg_ack_plan_dev(self.ctx, C.byref(b), stream), "rxg_ack_plan_dev")
+
+    def acks_attach(self, acks_host: int, frames_host: int, stride: int, nacks: int):
+        """rxg_acks_attach: host copies (addresses) of an ack_plan_dev call's acks and of the frames
+        built from its segs (ACK a at frames_host + a * stride) for the next rx replay and the
+        time after it; the caller keeps them alive until the replay after that, the next attach
+        or fini."""
+        _check(_lib.rxg_acks_attach(self.ctx, acks_host, frames_host, stride, nacks), "rxg_acks_attach")
+
+    def ack_take(self, tcb_idx: int, snd_nxt: int, rcv_ack: int):
+        """rxg_ack_take: the address of the prebuilt ACK frame of tcb_idx, or None when there is
+        none the stack may send (see rxg.h)."""
+        p = C.c_void_p()
+        rc = _lib.rxg_ack_take(self.ctx, tcb_idx, snd_nxt & 0xFFFFFFFF, rcv_ack & 0xFFFFFFFF, C.byref(p))
+        _check(min(rc, 0), "rxg_ack_take")
+        return p.value if rc == 1 else None
 
     def flow_trains_attach(self, order_host: int, nseg: int, trains_host: int, ntrains: int):
         """rxg_flow_trains_attach: host copies (addresses) of a flow_trains_dev call's order and trains

@@ -1260,6 +1260,167 @@ int rxg_train_payload_host(const void *recs, uint32_t rec_kind, void *const *fra
                            uint64_t *arena_used);
 
 /* ------------------------------------------------------------------------- */
+/* A burst's ACKs planned per flow: one rxg_tx_seg per flow that received      */
+/* data, and where the connection negotiated timestamps that ACK's option      */
+/* block, both in the form rxg_tx_build_opt_dev takes.  The reference answers  */
+/* once per poll, not per segment: tcp_established sets need_ack_now for a     */
+/* segment with data or FIN (tcp_states.c:119-120) and the socket loop then    */
+/* sends ptcb->tcp_flags = TCP_FLAG_ACK; sendtcpdata(ptcb, NULL, 0)            */
+/* (socket_interface.c:214-218): a 20-byte TCP header, sent_seq = next_seq,    */
+/* recv_ack = ptcb->ack, rx_win 12000 unswapped (tcp_out.c:157-207).  One ACK  */
+/* per flow and burst that carries the flow's final ptcb->ack is that          */
+/* coalescing.  Whether an ACK is sent stays the stack's decision, taken       */
+/* against its own state at send time (rxg_ack_take below).                    */
+/*                                                                             */
+/* Inputs.  order, cap_seg, trains, cap_trains and train_count are the outputs */
+/* of rxg_flow_trains_dev / _host for the burst of n frames; S' and T' are     */
+/* rxg_train_payload_dev's: S' = min(train_count[0], cap_seg, n), T' =         */
+/* min(train_count[1], cap_trains, n), T' = 0 when S' == 0.  rxopts (may be    */
+/* NULL) are rxg_rx_opts_dev's n records for the same burst.  state[ntcb] is   */
+/* the caller's table of rxg_ack_state, one entry per TCB.                     */
+/*                                                                             */
+/* Which flows get an ACK.  A flow is a maximal run of trains k < T' with one  */
+/* tcb_idx (trains stand in tcb_idx order); its first train h is the one with  */
+/* the lowest k, found by comparing train k with train k - 1:                  */
+/* RXG_FTR_FLOW_FIRST is not trusted, so no list of trains gives one flow two  */
+/* ACKs.  A flow whose tcb_idx is outside [0, ntcb) is counted in count[2] and */
+/* its state is never read.  A flow whose state lacks RXG_AS_LIVE is counted   */
+/* in count[1].  Every other flow gets an ACK; ACK a belongs to the a-th such  */
+/* flow in train order.                                                        */
+/*                                                                             */
+/* The ACK's values.  If h carries RXG_FTR_HEAD: ack = trains[h].next_ack,     */
+/* flagged RXG_ACK_ADVANCES, and RXG_ACK_FIN too when h carries RXG_FTR_FIN.   */
+/* Otherwise ack = state.rcv_ack, flagged RXG_ACK_DUP: the burst brought the   */
+/* flow nothing the window takes in order, the answer is a duplicate ACK.      */
+/* seq = state.snd_nxt, win_raw = state.win_raw, tcp_flags = RXG_TCP_FLAG_ACK, */
+/* data_len = 0, src_off = 0, pad = 0, flow = tcb_idx (the build's rxg_tx_flow */
+/* table is indexed by TCB), ip_id = (uint16_t)(ip_id0 + a).                   */
+/*                                                                             */
+/* Options.  opts (may be NULL) is a table of opt_cap blocks the call writes   */
+/* into; its first opt_base entries are the caller's own constant blocks and   */
+/* are never touched.  opt_plain is 0..opt_base: 0 for sendtcpdata's 20-byte   */
+/* header, or the 1-based index of a preloaded rxg_tx_opt_ref_ack block for    */
+/* sendack's (tcp_out.c:350).  For a flow without RXG_AS_TS, or with opts      */
+/* NULL, reserved = opt_plain.  For a flow with RXG_AS_TS: if opt_base + a <   */
+/* opt_cap, opts[opt_base + a] is written as rxg_tx_opt_timestamp(tsval_now,   */
+/* tsecr) writes it (len 12, the twelve bytes, every other byte of the 48      */
+/* zero) and reserved = opt_base + a + 1; otherwise no block is written,       */
+/* reserved = opt_plain, the ACK (valid without the echo) is flagged           */
+/* RXG_ACK_NO_OPT and counted in count[3].  tsecr is the tsval of the HEAD     */
+/* train's FIRST segment when the flow ADVANCES, rxopts is given, that segment */
+/* -- packet order[trains[h].first], with trains[h].first < S' and the packet  */
+/* < n -- has a record with RXG_O_TS: RFC 7323 section 4.3, an ACK for several */
+/* segments echoes the earliest, the one that covers Last.ACK.sent.  In every  */
+/* other case tsecr = state.ts_recent, and neither order nor rxopts is indexed */
+/* out of range.  PAWS and the update of ts_recent stay the stack's.           */
+/*                                                                             */
+/* Outputs.  segs[a] (all 32 bytes defined) and acks[a] for a < cap; an ACK at */
+/* or past cap writes neither them nor its option block, but is counted.       */
+/* count is 4 words, WRITTEN: ACKs needed whatever cap is, flows not LIVE,     */
+/* flows out of range, ACKs without their option block (whatever cap is).      */
+/* n == 0 or T' == 0: count = {0, 0, 0, 0} and nothing else.  The output is a  */
+/* pure function of the arguments: never of the grid, the stream, a mirror or  */
+/* an earlier call.                                                            */
+/*                                                                             */
+/* Deliberately not in this call: SACK blocks (they need the window's pending  */
+/* pairs, more per-connection state than a table of words); bare FINs without  */
+/* data (no segment of any train: the stack acknowledges them itself);         */
+/* delayed-ACK timing; frames (rxg_tx_build_opt_dev makes them from segs,      */
+/* opts and a rxg_tx_flow table indexed by TCB, n = min(count[0], cap)).       */
+/* ------------------------------------------------------------------------- */
+typedef struct rxg_ack_state {   /* 16 bytes, tables 16-byte aligned */
+    uint32_t snd_nxt;     /* ptcb->next_seq, host order                                       */
+    uint32_t rcv_ack;     /* ptcb->ack as it stands before the burst                          */
+    uint32_t ts_recent;   /* echoed when the burst gives no newer value                       */
+    uint16_t win_raw;     /* stored unswapped, as tcp_out.c:190 (12000 = the reference's)     */
+    uint16_t flags;       /* RXG_AS_*                                                         */
+} rxg_ack_state;
+#define RXG_AS_LIVE 0x1u  /* this TCB gets ACKs          */
+#define RXG_AS_TS   0x2u  /* timestamps were negotiated  */
+
+typedef struct rxg_ack {         /* 16 bytes, arrays 16-byte aligned */
+    int32_t  tcb_idx;
+    uint32_t ack, seq;    /* what segs[a] carries                                             */
+    uint32_t flags_train; /* RXG_ACK_* in the low byte, the low 24 bits of h above them       */
+} rxg_ack;
+#define RXG_ACK_ADVANCES 0x01u /* ack is the HEAD train's next_ack                    */
+#define RXG_ACK_DUP      0x02u /* ack is state.rcv_ack: a duplicate ACK               */
+#define RXG_ACK_FIN      0x04u /* the acknowledged train ends in a FIN                */
+#define RXG_ACK_NO_OPT   0x08u /* a timestamp flow whose block did not fit opt_cap    */
+
+/* Asynchronous on `stream`, three launches: a lane per train decides whether the train is its
+   flow's first and what becomes of the flow, with per-tile (256 trains) sums of ACKs, flows
+   not LIVE and flows out of range; one workgroup scans the tile sums (rounds of 256 tiles
+   with a carry) and writes count[0..2] and count[3] = 0; a lane per train again ranks its
+   flow inside the tile on the tile's base and writes segs[a], acks[a] and the option block
+   with 16-byte stores, adding its tile's ACKs without a block to count[3] (the one atomic:
+   it decides no position).  No workgroup waits on another; train_count is read on the
+   device only; rxg_config.max_blocks caps the grids and the output does not depend on them.
+   The context owns the scratch (16 bytes per tile), grown on demand; one call at a time
+   uses it, as for rxg_flow_trains_dev.
+   -EINVAL: a NULL ctx, p, train_count, state or count; order NULL with cap_seg != 0, trains
+   NULL with cap_trains != 0, segs or acks NULL with cap != 0; state, rxopts, opts, segs or
+   acks not 16-, trains, train_count or count not 8-, order not 4-byte aligned; opt_plain >
+   opt_base; opt_base > opt_cap; ntcb 0 or over RXG_FS_MAX_NTCB; flags != 0 (none is
+   defined).  -ENOMEM: the scratch cannot be allocated; nothing is launched then.  A group's
+   members are plain contexts for this call. */
+typedef struct rxg_dev_ack_plan {
+    const uint32_t *order;        /* dev: rxg_flow_trains_dev's order, cap_seg entries           */
+    uint64_t cap_seg;
+    const rxg_flow_train *trains; /* dev: its trains, cap_trains entries                         */
+    uint64_t cap_trains;
+    const uint64_t *train_count;  /* dev: its 4 count words, read on the device                  */
+    uint32_t n;                   /* the burst's frames                                          */
+    uint32_t ntcb;                /* 1 .. RXG_FS_MAX_NTCB: entries of state                      */
+    const rxg_rx_opt *rxopts;     /* dev: rxg_rx_opts_dev's n records; may be NULL               */
+    const rxg_ack_state *state;   /* dev, 16-byte aligned, ntcb entries                          */
+    uint32_t flags;               /* 0                                                           */
+    uint32_t tsval_now;           /* the TSval every written block carries                       */
+    uint16_t ip_id0;
+    uint16_t pad0;
+    uint32_t opt_plain;           /* 0 .. opt_base                                               */
+    uint32_t opt_base, opt_cap;   /* opt_base <= opt_cap                                         */
+    rxg_tx_opt *opts;             /* dev, 16-byte aligned, opt_cap blocks; may be NULL           */
+    rxg_tx_seg *segs;             /* dev, 16-byte aligned, cap entries                           */
+    rxg_ack *acks;                /* dev, 16-byte aligned, cap entries                           */
+    uint64_t cap;
+    uint64_t *count;              /* dev, 4 words, WRITTEN                                       */
+} rxg_dev_ack_plan;
+int rxg_ack_plan_dev(rxg_ctx *ctx, const rxg_dev_ack_plan *p, void *stream);
+
+/* Host form of the rule (no context, no GPU), for host-buffer bursts: the same struct with
+   every pointer naming host memory (natural alignment suffices).  Returns 0; -EINVAL: the
+   device call's list without the alignments. */
+int rxg_ack_plan_host(const rxg_dev_ack_plan *p);
+
+/* Using the prebuilt ACKs.  rxg_acks_attach names host copies of a call's `acks` (nacks =
+   min(count[0], cap) entries, tcb_idx strictly ascending: attach verifies that) and of the
+   frames built from its segs (ACK a at frames_host + a * stride) for the burst the next
+   rxg_rx_replay call on this context replays.  Unlike the other attachments this one
+   OUTLIVES that replay: the reference sends its ACK after the segments were handled
+   (socket_interface.c:214).  It ends at the rxg_rx_replay after that one, at the next
+   rxg_acks_attach, or at rxg_fini -- and with its own replay if that replay returns an
+   error, from its argument checks or later: ACKs of a burst that was not replayed whole are
+   never handed out.
+   rxg_ack_take is called from the stack's ACK send, during that replay or after it
+   returned, with the TCB and the stack's own next_seq and ack.  It returns 1 and sets
+   *frame_out to the prebuilt frame exactly when (1) an attached ACK exists for tcb_idx;
+   (2) its seq and ack equal snd_nxt and rcv_ack: a prebuilt ACK that no longer says what
+   the stack's state says is never sent -- segments PushData refused, a handler that sent
+   data meanwhile, a HEAD promise the caller voided; (3) the replay neither re-classified a
+   packet to or from that TCB nor absorbed a mirror write to that slot (rxg_tcb_upsert /
+   _remove / _set_state / _load, by a handler or between the burst and its replay), and no
+   such write was made since the replay returned.  Writes after the replay are known until
+   the next burst is launched on this context (its launch starts a new write log): call
+   rxg_ack_take before that launch, or the seq / ack comparison alone stands between a slot
+   that was given to another connection meanwhile and the old connection's frame.  It
+   returns 0 otherwise, and before the replay has begun: the stack then builds its own ACK.
+   -EINVAL: ctx or frame_out NULL (attach: ctx NULL, a NULL array or stride 0 with nacks
+   != 0, tcb_idx not strictly ascending). */
+int rxg_acks_attach(rxg_ctx *ctx, const rxg_ack *acks_host, void *frames_host, uint32_t stride, uint64_t nacks);
+int rxg_ack_take(rxg_ctx *ctx, int32_t tcb_idx, uint32_t snd_nxt, uint32_t rcv_ack, void **frame_out);
+
+/* ------------------------------------------------------------------------- */
 /* Counters                                                                   */
 /* ------------------------------------------------------------------------- */
 int rxg_counters_reset(rxg_ctx *ctx, void *stream);
