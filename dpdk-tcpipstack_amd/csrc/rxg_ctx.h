@@ -9,7 +9,9 @@
 //                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
 //   rxg_replay.cpp  the per-packet replay into the caller's handlers, the payload hand-off,
-//                   ether_in
+//                   what a replay hands out (ReplayAttached below), ether_in
+//   rxg_replaylog.h which packets a table write made stale and how each is fixed (WriteSet,
+//                   ReplayLog): HIP-free
 //   rxg_util.cpp    synthetic frames, memory and event helpers
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +32,7 @@
 #include "rxg_mirror.h"
 #include "rxg_opqueue.h"
 #include "rxg_packpool.h"
+#include "rxg_replaylog.h"
 #include "rxg_srvfsm.h"
 #include "rxg_tablesync.h"
 
@@ -145,6 +148,67 @@ struct SerialScratch {
 enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridFlowTrain,
               kGridTrainPay, kGridAckPlan, kGridOps };
 
+// What a replay hands out to the handlers it calls: host copies the caller attached for the
+// replay that follows, answered for the packet being replayed (pos).
+struct ReplayAttached {
+    int64_t pos = -1;  // packet whose handlers rxg_rx_replay is running
+    // rxg_reset_attach: a call's resets and their packet indices, and rxg_reset_take's cursor
+    uint8_t *rst_host = nullptr;
+    const uint32_t *rst_idx = nullptr;
+    uint64_t rst_n = 0, rst_cur = 0;
+    // rxg_rx_opts_attach: a rxg_rx_opts_dev call's records; rxg_rx_opt_current answers from them
+    const rxg_rx_opt *opt_host = nullptr;
+    uint32_t opt_n = 0;
+    bool opt_live = false;  // the running replay's burst has opt_n frames
+    // rxg_flow_sums_attach: a call's summaries; rxg_flow_sum_current answers from them
+    const rxg_flow_sum *fs_host = nullptr;
+    uint64_t fs_m = 0;
+    // rxg_flow_trains_attach: a call's order and trains; rxg_flow_train_current answers from them
+    const uint32_t *ft_order = nullptr;
+    const rxg_flow_train *ft_trains = nullptr;
+    uint64_t ft_nseg = 0, ft_ntrains = 0;
+    // rxg_acks_attach: a call's acks and the frames built from its segs.  ak_phase 1: attached,
+    // waiting for its replay; 2: that replay has begun (rxg_ack_take answers, also after it
+    // returned); the next replay, attach or fini ends it.  What the replay saw that voids a
+    // prebuilt ACK: the TCBs a re-classification took a packet from or gave one to, the tuples of
+    // written slots (the replay's own write log), a whole-table change
+    const rxg_ack *ak_acks = nullptr;
+    uint8_t *ak_frames = nullptr;
+    uint64_t ak_n = 0;
+    uint32_t ak_stride = 0, ak_phase = 0;
+    std::unordered_set<int32_t> ak_void_tcb;
+    std::unordered_set<rxg::TupleKey, rxg::TupleKeyHash> ak_void_keys;
+    bool ak_void_all = false;
+
+    // no packet is being replayed, and what was attached for this replay is no longer named
+    // (the ACKs outlive it: acks_detach)
+    void end_of_replay()
+    {
+        pos = -1;
+        rst_host = nullptr;
+        rst_idx = nullptr;
+        rst_n = rst_cur = 0;
+        opt_host = nullptr;
+        opt_n = 0;
+        opt_live = false;
+        fs_host = nullptr;
+        fs_m = 0;
+        ft_order = nullptr;
+        ft_trains = nullptr;
+        ft_nseg = ft_ntrains = 0;
+    }
+    void acks_detach()
+    {
+        ak_acks = nullptr;
+        ak_frames = nullptr;
+        ak_n = 0;
+        ak_stride = ak_phase = 0;
+        ak_void_tcb.clear();
+        ak_void_keys.clear();
+        ak_void_all = false;
+    }
+};
+
 struct rxg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -175,12 +239,9 @@ struct rxg_ctx {
 
     // mirror changes since the last clear, for rxg_rx_replay's re-classification
     uint64_t gen = 0;
-    std::vector<rxg::TupleKey> touched_keys;  // tuples (old and new) of changed slots
-    std::vector<int32_t> touched_listen; // dports whose LISTENING slots changed (pass 2)
-    bool touched_all = false;            // whole table replaced
-    bool touched_pass2 = false;          // min_null moved (the pass-2 NULL-slot flag)
-    bool replay_on_device = false;       // RXG_CFG_REPLAY_ON_DEVICE
-    uint64_t rp_stats[4] = {0, 0, 0, 0}; // marked, host fix-ups, device fix-ups, launches
+    rxg::WriteSet touched;
+    bool replay_on_device = false;  // RXG_CFG_REPLAY_ON_DEVICE
+    rxg::ReplayLog replay;          // the running (or last) replay's staleness rule and records
 
     // the last burst's device batch (re-classification reads it again)
     // The last launch's bursts (one, or several of one frame pool: rxg_rx_bursts_dev) and
@@ -196,9 +257,7 @@ struct rxg_ctx {
     uint32_t replay_cursor = 0;
     // writes absorbed by the replays of this launch's earlier bursts (they came after every
     // burst of the launch was classified)
-    std::vector<rxg::TupleKey> launch_keys;
-    std::vector<int32_t> launch_listen;
-    bool launch_all = false, launch_pass2 = false;
+    rxg::WriteSet launch_writes;
     const uint8_t *last_frames = nullptr;
     const uint32_t *last_off = nullptr;  // nullptr: a fixed-stride burst (burst_offsets)
     uint32_t last_slot0 = 0, last_stride64 = 0;
@@ -224,67 +283,33 @@ struct rxg_ctx {
     uint32_t h_pm_cap = 0, pm_n = 0;
     bool pm_pending = false;  // h_pm not fetched yet for this gather
     hipEvent_t pm_ev = nullptr;
-    int64_t replay_pos = -1;  // packet whose handlers rxg_rx_replay is running
+    ReplayAttached attached;  // what the replay hands out, and the packet it is at
 
     // rxg_tx_reset_dev: the slice counts its three launches share (buf[0])
     SerialScratch rst{"rxg_tx_reset_dev"};
     // rxg_tx_plan_dev: the tile sums its launches share (buf[0])
     SerialScratch txp{"rxg_tx_plan_dev"};
-    // rxg_reset_attach: host copies of a call's resets and their packet indices for the replay
-    // that follows (cleared when it returns), and rxg_reset_take's cursor into them
-    uint8_t *rst_host = nullptr;
-    const uint32_t *rst_idx = nullptr;
-    uint64_t rst_n = 0, rst_cur = 0;
-    // rxg_rx_opts_attach: a host copy of a rxg_rx_opts_dev call's records for the replay that
-    // follows (cleared when it returns); rxg_rx_opt_current answers from it
-    const rxg_rx_opt *opt_host = nullptr;
-    uint32_t opt_n = 0;
-    bool opt_live = false;  // the running replay's burst has opt_n frames
     // rxg_flow_sums_dev: the dense accumulator and the touched bitmap (all zero between calls)
     // and the tile counts (buf[kFsAcc .. kFsTiles])
     enum { kFsAcc, kFsBits, kFsTiles };
     SerialScratch fs{"rxg_flow_sums_dev"};
     bool fs_dirty = false;  // a launch failed part-way: both are zeroed again before the next
-    // rxg_flow_sums_attach: a host copy of a call's summaries for the replay that follows
-    // (cleared when it returns); rxg_flow_sum_current answers from it
-    const rxg_flow_sum *fs_host = nullptr;
-    uint64_t fs_m = 0;
 
     // rxg_flow_trains_dev: the pairs' two buffers, the segments' meta and the trains' starts, and
     // the counts its launches hand on (buf[kFtPairs .. kFtCounts]); no content is kept
     enum { kFtPairs, kFtMeta, kFtCounts };
     SerialScratch ft{"rxg_flow_trains_dev"};
-    // rxg_flow_trains_attach: host copies of a call's order and trains for the replay that
-    // follows (cleared when it returns); rxg_flow_train_current answers from them
-    const uint32_t *ft_order = nullptr;
-    const rxg_flow_train *ft_trains = nullptr;
-    uint64_t ft_nseg = 0, ft_ntrains = 0;
+
     // rxg_train_payload_dev: the trains' offsets and the tile sums (buf[0]); no content is kept
     SerialScratch tp{"rxg_train_payload_dev"};
     // rxg_ack_plan_dev: the tile sums (buf[0]); no content is kept
     SerialScratch ak{"rxg_ack_plan_dev"};
-    // rxg_acks_attach: host copies of a call's acks and of the frames built from its segs.  ak_phase
-    // 1: attached, waiting for its replay; 2: that replay has begun (rxg_ack_take answers, also
-    // after it returned); the next replay, attach or fini ends it.  What the replay saw that voids
-    // a prebuilt ACK: the TCBs a re-classification took a packet from or gave one to, the tuples
-    // of written slots (the replay's own write log), a whole-table change
-    const rxg_ack *ak_acks = nullptr;
-    uint8_t *ak_frames = nullptr;
-    uint64_t ak_n = 0;
-    uint32_t ak_stride = 0, ak_phase = 0;
-    std::unordered_set<int32_t> ak_void_tcb;
-    std::unordered_set<rxg::TupleKey, rxg::TupleKeyHash> ak_void_keys;
-    bool ak_void_all = false;
 
     // ARP mirror (host set + device open-addressing table, rxg_mirror.h)
     bool arp_enabled = false;
     rxg::ArpMirror arp;
     std::unordered_map<uint32_t, int> arp_since_burst;  // learned after the last burst
 
-    // replay scratch, kept across calls
-    std::vector<rxg_rec16> rp_cur;
-    std::vector<uint32_t> rp_seq;
-    std::vector<uint64_t> rp_filter;
     const uint64_t *pm_used = nullptr;  // the gather's arena_used (device)
     bool pm_poisoned = false;           // that gather timed out: no payload is handed out
 

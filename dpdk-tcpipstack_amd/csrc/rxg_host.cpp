@@ -217,8 +217,8 @@ static void note_slot(rxg_ctx *c, int32_t idx)
     if (idx >= c->mir.ntcb() || !c->mir.live[idx]) return;
     const rxg_tcb_tuple &t = c->mir.tcb[idx];
     TupleKey k;
-    if (tcb_key(t, k)) c->touched_keys.push_back(k);
-    if (t.state == RXG_LISTENING && port_in_range(t.dport)) c->touched_listen.push_back(t.dport);
+    if (tcb_key(t, k)) c->touched.keys.push_back(k);
+    if (t.state == RXG_LISTENING && port_in_range(t.dport)) c->touched.listen.push_back(t.dport);
 }
 
 extern "C" int rxg_tcb_upsert(rxg_ctx *c, int32_t idx, const rxg_tcb_tuple *t)
@@ -232,7 +232,7 @@ extern "C" int rxg_tcb_upsert(rxg_ctx *c, int32_t idx, const rxg_tcb_tuple *t)
     note_slot(c, idx);  // the new ones
     // NULL slots appearing (old Ntcb .. idx-1) or disappearing (a removed slot reused) move
     // min_null, the pass-2 NULL-slot flag of later packets
-    if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched_pass2 = true;
+    if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched.pass2 = true;
     c->tables.tcb_changed();
     c->gen++;
     return 0;
@@ -246,7 +246,7 @@ extern "C" int rxg_tcb_remove(rxg_ctx *c, int32_t idx)
     const int32_t min_null = c->mir.min_null;
     note_slot(c, idx);
     c->mir.remove(idx);
-    if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched_pass2 = true;
+    if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched.pass2 = true;
     if ((size_t)idx < c->rcv_state.size()) c->rcv_state[idx] = 0;  // FreeWindow
     c->tables.tcb_changed();
     c->gen++;
@@ -276,7 +276,7 @@ extern "C" int rxg_tcb_load(rxg_ctx *c, const rxg_tcb_tuple *tcbs, const uint8_t
             return fail(-EINVAL, "rxg_tcb_load: slot %d state %u", i, tcbs[i].state);
     c->mir.load(tcbs, live, ntcb);
     c->tables.tcb_changed();
-    c->touched_all = true;
+    c->touched.all = true;
     c->gen++;
     c->rcv_cur.clear();
     c->rcv_state.clear();
@@ -295,7 +295,7 @@ extern "C" int rxg_flow_partition(rxg_ctx *c, uint32_t part, uint32_t nparts)
     c->mir.nparts = nparts;
     c->mir.need_rebuild = true;  // the whole table, as after rxg_tcb_load
     c->tables.tcb_changed();
-    c->touched_all = true;
+    c->touched.all = true;
     c->gen++;
     return 0;
 }
@@ -534,12 +534,8 @@ int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, ui
     if (c->last_bursts.empty()) c->last_bursts.push_back({nullptr, nullptr, 0u, nullptr});
     select_burst(c, 0);
     // the records reflect the mirror as of now: changes are tracked from here (replay)
-    c->touched_keys.clear();
-    c->touched_listen.clear();
-    c->touched_all = c->touched_pass2 = false;
-    c->launch_keys.clear();
-    c->launch_listen.clear();
-    c->launch_all = c->launch_pass2 = false;
+    c->touched.clear();
+    c->launch_writes.clear();
     return 0;
 }
 

@@ -108,7 +108,7 @@ extern "C" int rxg_rcv_set(rxg_ctx *c, int32_t idx, uint32_t cur_seq, uint32_t p
 extern "C" int rxg_payload_take(rxg_ctx *c, int32_t idx, uint32_t seq, uint32_t length, rxg_payload_msg *msg)
 {
     if (!c) return fail(-EINVAL, "rxg_payload_take: ctx NULL");
-    const int64_t pos = c->replay_pos;
+    const int64_t pos = c->attached.pos;
     if (pos < 0 || (uint64_t)pos >= c->pm_n || length == 0 || length > 0xFFFFu) return 0;
     if (c->pm_pending) {  // first take after the gather: fetch the burst's descriptors
         if (int rc = set_device(c)) return rc;
@@ -148,10 +148,11 @@ extern "C" int rxg_reset_attach(rxg_ctx *c, void *resets_host, const uint32_t *i
 {
     if (!c || (nbuilt && (!resets_host || !idx_host)))
         return fail(-EINVAL, "rxg_reset_attach: NULL argument");
-    c->rst_host = nbuilt ? (uint8_t *)resets_host : nullptr;
-    c->rst_idx = nbuilt ? idx_host : nullptr;
-    c->rst_n = nbuilt;
-    c->rst_cur = 0;
+    ReplayAttached &a = c->attached;
+    a.rst_host = nbuilt ? (uint8_t *)resets_host : nullptr;
+    a.rst_idx = nbuilt ? idx_host : nullptr;
+    a.rst_n = nbuilt;
+    a.rst_cur = 0;
     return 0;
 }
 
@@ -162,11 +163,12 @@ extern "C" int rxg_reset_attach(rxg_ctx *c, void *resets_host, const uint32_t *i
 extern "C" int rxg_reset_take(rxg_ctx *c, uint16_t ip_id, void **frame_out)
 {
     if (!c || !frame_out) return fail(-EINVAL, "rxg_reset_take: NULL argument");
-    const int64_t pos = c->replay_pos;
-    if (pos < 0 || !c->rst_host) return 0;
-    while (c->rst_cur < c->rst_n && (int64_t)c->rst_idx[c->rst_cur] < pos) ++c->rst_cur;
-    if (c->rst_cur >= c->rst_n || (int64_t)c->rst_idx[c->rst_cur] != pos) return 0;
-    uint8_t *f = c->rst_host + 64u * c->rst_cur;
+    ReplayAttached &a = c->attached;
+    const int64_t pos = a.pos;
+    if (pos < 0 || !a.rst_host) return 0;
+    while (a.rst_cur < a.rst_n && (int64_t)a.rst_idx[a.rst_cur] < pos) ++a.rst_cur;
+    if (a.rst_cur >= a.rst_n || (int64_t)a.rst_idx[a.rst_cur] != pos) return 0;
+    uint8_t *f = a.rst_host + 64u * a.rst_cur;
     if ((uint16_t)(f[18] | (f[19] << 8)) != ip_id) rxg_reset_set_id(f, ip_id);
     *frame_out = f;
     return 1;
@@ -176,19 +178,20 @@ extern "C" int rxg_reset_take(rxg_ctx *c, uint16_t ip_id, void **frame_out)
 extern "C" int rxg_rx_opts_attach(rxg_ctx *c, const rxg_rx_opt *opts_host, uint32_t n)
 {
     if (!c || (n && !opts_host)) return fail(-EINVAL, "rxg_rx_opts_attach: NULL argument");
-    c->opt_host = n ? opts_host : nullptr;
-    c->opt_n = n;
+    c->attached.opt_host = n ? opts_host : nullptr;
+    c->attached.opt_n = n;
     return 0;
 }
 
-// Record replay_pos of the attached copy: options do not depend on the mirror, so the record
-// of a packet the replay re-classified is as good as any other's.
+// The record of the attached copy for the packet being replayed: options do not depend on the
+// mirror, so the record of a packet the replay re-classified is as good as any other's.
 extern "C" int rxg_rx_opt_current(rxg_ctx *c, const rxg_rx_opt **out)
 {
     if (!c || !out) return fail(-EINVAL, "rxg_rx_opt_current: NULL argument");
-    const int64_t pos = c->replay_pos;
-    if (pos < 0 || !c->opt_host || !c->opt_live || pos >= (int64_t)c->opt_n) return 0;
-    *out = c->opt_host + pos;
+    const ReplayAttached &a = c->attached;
+    const int64_t pos = a.pos;
+    if (pos < 0 || !a.opt_host || !a.opt_live || pos >= (int64_t)a.opt_n) return 0;
+    *out = a.opt_host + pos;
     return 1;
 }
 
@@ -200,21 +203,22 @@ extern "C" int rxg_flow_sums_attach(rxg_ctx *c, const rxg_flow_sum *sums_host, u
         if (sums_host[k].tcb_idx <= sums_host[k - 1].tcb_idx)
             return fail(-EINVAL, "rxg_flow_sums_attach: entry %llu is not above its predecessor's tcb_idx",
                         (unsigned long long)k);
-    c->fs_host = m ? sums_host : nullptr;
-    c->fs_m = m;
+    c->attached.fs_host = m ? sums_host : nullptr;
+    c->attached.fs_m = m;
     return 0;
 }
 
-// The packet being replayed, if its record is still the burst's (rp_seq 0: not re-classified)
-// and a DISPATCH to a flow of the attached list that covers its index.
+// The packet being replayed, if its record is still the burst's (ReplayLog::as_burst: not
+// re-classified) and a DISPATCH to a flow of the attached list that covers its index.
 extern "C" int rxg_flow_sum_current(rxg_ctx *c, const rxg_flow_sum **out, uint32_t *pkt_idx)
 {
     if (!c || !out || !pkt_idx) return fail(-EINVAL, "rxg_flow_sum_current: NULL argument");
-    const int64_t pos = c->replay_pos;
-    if (pos < 0 || !c->fs_host || (uint64_t)pos >= c->rp_cur.size() || (uint64_t)pos >= c->rp_seq.size()) return 0;
-    const rxg_rec16 &r = c->rp_cur[(size_t)pos];
-    if (c->rp_seq[(size_t)pos] != 0u || r.verdict != RXG_V_DISPATCH) return 0;
-    const rxg_flow_sum *lo = c->fs_host, *hi = c->fs_host + c->fs_m;
+    const ReplayAttached &a = c->attached;
+    const int64_t pos = a.pos;
+    if (pos < 0 || !a.fs_host || (uint64_t)pos >= c->replay.size()) return 0;
+    const rxg_rec16 &r = c->replay.record((size_t)pos);
+    if (!c->replay.as_burst((size_t)pos) || r.verdict != RXG_V_DISPATCH) return 0;
+    const rxg_flow_sum *lo = a.fs_host, *hi = a.fs_host + a.fs_m;
     const rxg_flow_sum *s =
         std::lower_bound(lo, hi, r.tcb_idx, [](const rxg_flow_sum &e, int32_t t) { return e.tcb_idx < t; });
     if (s == hi || s->tcb_idx != r.tcb_idx || (uint64_t)pos < s->first_idx || (uint64_t)pos > s->last_idx) return 0;
@@ -238,57 +242,46 @@ extern "C" int rxg_flow_trains_attach(rxg_ctx *c, const uint32_t *order_host, ui
                         (unsigned long long)k, t.first, t.nseg, (unsigned long long)at);
         at += t.nseg;
     }
-    c->ft_order = nseg ? order_host : nullptr;
-    c->ft_trains = ntrains ? trains_host : nullptr;
-    c->ft_nseg = nseg;
-    c->ft_ntrains = ntrains;
+    ReplayAttached &a = c->attached;
+    a.ft_order = nseg ? order_host : nullptr;
+    a.ft_trains = ntrains ? trains_host : nullptr;
+    a.ft_nseg = nseg;
+    a.ft_ntrains = ntrains;
     return 0;
 }
 
-// The packet being replayed, if its record is still the burst's (rp_seq 0: not re-classified)
-// and a DISPATCH: the attached trains of its flow are found by tcb_idx, the packet among the
-// flow's segments (ascending packet indices), and its train by that position.
+// The packet being replayed, if its record is still the burst's (ReplayLog::as_burst: not
+// re-classified) and a DISPATCH: the attached trains of its flow are found by tcb_idx, the packet
+// among the flow's segments (ascending packet indices), and its train by that position.
 extern "C" int rxg_flow_train_current(rxg_ctx *c, const rxg_flow_train **out, uint32_t *pos_out)
 {
     if (!c || !out || !pos_out) return fail(-EINVAL, "rxg_flow_train_current: NULL argument");
-    const int64_t pos = c->replay_pos;
-    if (pos < 0 || !c->ft_order || !c->ft_trains || (uint64_t)pos >= c->rp_cur.size() ||
-        (uint64_t)pos >= c->rp_seq.size())
-        return 0;
-    const rxg_rec16 &r = c->rp_cur[(size_t)pos];
-    if (c->rp_seq[(size_t)pos] != 0u || r.verdict != RXG_V_DISPATCH) return 0;
-    const rxg_flow_train *lo = c->ft_trains, *hi = c->ft_trains + c->ft_ntrains;
+    const ReplayAttached &a = c->attached;
+    const int64_t pos = a.pos;
+    if (pos < 0 || !a.ft_order || !a.ft_trains || (uint64_t)pos >= c->replay.size()) return 0;
+    const rxg_rec16 &r = c->replay.record((size_t)pos);
+    if (!c->replay.as_burst((size_t)pos) || r.verdict != RXG_V_DISPATCH) return 0;
+    const rxg_flow_train *lo = a.ft_trains, *hi = a.ft_trains + a.ft_ntrains;
     const rxg_flow_train *tl =
         std::lower_bound(lo, hi, r.tcb_idx, [](const rxg_flow_train &e, int32_t t) { return e.tcb_idx < t; });
     const rxg_flow_train *th =
         std::upper_bound(tl, hi, r.tcb_idx, [](int32_t t, const rxg_flow_train &e) { return t < e.tcb_idx; });
     if (tl == th) return 0;
-    const uint64_t a = tl->first, b = std::min<uint64_t>((uint64_t)(th - 1)->first + (th - 1)->nseg, c->ft_nseg);
-    if (a >= b) return 0;
-    const uint32_t *seg = std::lower_bound(c->ft_order + a, c->ft_order + b, (uint32_t)pos);
-    if (seg == c->ft_order + b || *seg != (uint32_t)pos) return 0;
-    const uint64_t q = (uint64_t)(seg - c->ft_order);
+    const uint64_t s0 = tl->first, s1 = std::min<uint64_t>((uint64_t)(th - 1)->first + (th - 1)->nseg, a.ft_nseg);
+    if (s0 >= s1) return 0;
+    const uint32_t *seg = std::lower_bound(a.ft_order + s0, a.ft_order + s1, (uint32_t)pos);
+    if (seg == a.ft_order + s1 || *seg != (uint32_t)pos) return 0;
+    const uint64_t q = (uint64_t)(seg - a.ft_order);
     // the last train of the flow that starts at or before q
     const rxg_flow_train *t =
         std::upper_bound(tl, th, q, [](uint64_t v, const rxg_flow_train &e) { return v < e.first; }) - 1;
-    if ((uint64_t)t->first + t->nseg > c->ft_nseg) return 0;  // order was capped inside this train
+    if ((uint64_t)t->first + t->nseg > a.ft_nseg) return 0;  // order was capped inside this train
     *out = t;
     *pos_out = (uint32_t)(q - t->first);
     return 1;
 }
 
 // ------------------------------------------------------------------ prebuilt ACKs ---
-static void acks_detach(rxg_ctx *c)
-{
-    c->ak_acks = nullptr;
-    c->ak_frames = nullptr;
-    c->ak_n = 0;
-    c->ak_stride = c->ak_phase = 0;
-    c->ak_void_tcb.clear();
-    c->ak_void_keys.clear();
-    c->ak_void_all = false;
-}
-
 extern "C" int rxg_acks_attach(rxg_ctx *c, const rxg_ack *acks_host, void *frames_host, uint32_t stride, uint64_t nacks)
 {
     if (!c || (nacks && (!acks_host || !frames_host || !stride)))
@@ -297,45 +290,39 @@ extern "C" int rxg_acks_attach(rxg_ctx *c, const rxg_ack *acks_host, void *frame
         if (acks_host[a].tcb_idx <= acks_host[a - 1].tcb_idx)
             return fail(-EINVAL, "rxg_acks_attach: entry %llu is not above its predecessor's tcb_idx",
                         (unsigned long long)a);
-    acks_detach(c);
+    ReplayAttached &a = c->attached;
+    a.acks_detach();
     if (!nacks) return 0;
-    c->ak_acks = acks_host;
-    c->ak_frames = (uint8_t *)frames_host;
-    c->ak_stride = stride;
-    c->ak_n = nacks;
-    c->ak_phase = 1;
+    a.ak_acks = acks_host;
+    a.ak_frames = (uint8_t *)frames_host;
+    a.ak_stride = stride;
+    a.ak_n = nacks;
+    a.ak_phase = 1;
     return 0;
 }
 
 // The attached ACK of tcb_idx, if it still says what the stack's state says and nothing voids
 // it: no packet re-classified to or from the TCB, no write to its slot (the slot's tuple is among
 // the written ones, or the slot is gone), no whole-table change -- in the replay, or since it
-// returned (the writes not yet absorbed: touched_keys / touched_all, kept until the next burst).
+// returned (the writes not yet absorbed: rxg_ctx::touched, kept until the next burst).
 extern "C" int rxg_ack_take(rxg_ctx *c, int32_t tcb_idx, uint32_t snd_nxt, uint32_t rcv_ack, void **frame_out)
 {
     if (!c || !frame_out) return fail(-EINVAL, "rxg_ack_take: NULL argument");
-    if (c->ak_phase != 2u || c->ak_void_all) return 0;
-    const rxg_ack *lo = c->ak_acks, *hi = c->ak_acks + c->ak_n;
+    const ReplayAttached &a = c->attached;
+    if (a.ak_phase != 2u || a.ak_void_all) return 0;
+    const rxg_ack *lo = a.ak_acks, *hi = a.ak_acks + a.ak_n;
     const rxg_ack *e = std::lower_bound(lo, hi, tcb_idx, [](const rxg_ack &x, int32_t t) { return x.tcb_idx < t; });
     if (e == hi || e->tcb_idx != tcb_idx || e->seq != snd_nxt || e->ack != rcv_ack) return 0;
     if (tcb_idx < 0 || tcb_idx >= c->mir.ntcb() || !c->mir.live[tcb_idx]) return 0;
     TupleKey k;
     if (!tcb_key(c->mir.tcb[tcb_idx], k)) return 0;
-    if (c->ak_void_tcb.count(tcb_idx) || c->ak_void_keys.count(k)) return 0;
-    if (c->touched_all || std::find(c->touched_keys.begin(), c->touched_keys.end(), k) != c->touched_keys.end()) return 0;
-    *frame_out = c->ak_frames + (size_t)(e - lo) * c->ak_stride;
+    if (a.ak_void_tcb.count(tcb_idx) || a.ak_void_keys.count(k)) return 0;
+    if (c->touched.all || std::find(c->touched.keys.begin(), c->touched.keys.end(), k) != c->touched.keys.end()) return 0;
+    *frame_out = a.ak_frames + (size_t)(e - lo) * a.ak_stride;
     return 1;
 }
 
 // ------------------------------------------------------------------------- replay ---
-static inline bool rec_is_tcp(const rxg_rec16 &r)
-{
-    return r.verdict == RXG_V_DISPATCH || r.verdict == RXG_V_RST_NOPCB || r.verdict == RXG_V_RST_LISTEN_NONSYN;
-}
-
-// A TCP record that findtcb pass 1 did not answer (listener or no TCB): pass 2 decides it.
-static inline bool rec_pass2(const rxg_rec16 &r) { return r.tcb_idx < 0 || (r.flags & RXG_F_LISTEN); }
-
 // Counter contributions of one TCP record (the kernel's definition; only the fields a
 // re-classification can change).
 static void tcp_record_counters(const rxg_rec16 &r, int64_t sign, int64_t *d)
@@ -347,38 +334,20 @@ static void tcp_record_counters(const rxg_rec16 &r, int64_t sign, int64_t *d)
     if (r.verdict == RXG_V_DISPATCH) d[RXG_C_DISPATCH] += sign;
 }
 
-// The pass-1 key of a frame of >= 54 bytes, as the kernel forms it: ports = dport << 16 |
-// sport (host order), ipv4_dst as loaded, ipv4_src host order (tcp_tcb.c:134-135,152-155).
-// The replay's written-tuple filter index (16 bits): every packet after a burst's first table
-// write is checked against it, so two multiplies rather than the table's seven (tuple_hash;
-// 14 -> 6 ns a packet on this container's core); a collision only costs the exact lookup.
-static inline uint32_t filter_hash(const TupleKey &k)
-{
-    return (k.ports * 0x9E3779B1u + k.src * 0x85EBCA6Bu + k.dst) >> 16;
-}
-
-static inline TupleKey frame_key(const uint8_t *f)
-{
-    const uint32_t sport = ((uint32_t)f[34] << 8) | f[35], dport = ((uint32_t)f[36] << 8) | f[37];
-    const uint32_t dst = (uint32_t)f[30] | ((uint32_t)f[31] << 8) | ((uint32_t)f[32] << 16) | ((uint32_t)f[33] << 24);
-    const uint32_t src = ((uint32_t)f[26] << 24) | ((uint32_t)f[27] << 16) | ((uint32_t)f[28] << 8) | f[29];
-    return TupleKey{(dport << 16) | sport, dst, src};
-}
-
 // Re-classify one TCP packet of >= 54 bytes against the table as it stands now, exactly as
 // rx_kernel's classify does (findtcb tcp_tcb.c:127-173, tcp_in.c:47-59), answered from the
 // host index the device mirror is patched from (rxg_mirror.h): the replay's fix-up of a
 // packet whose TCB a handler changed inside the burst.  The fields a
 // table change cannot move (checksums, datalen, flags of the frame) stay as the burst
 // computed them.
-static void host_classify(const rxg_ctx *c, const uint8_t *f, rxg_rec16 &r)
+static void host_classify(const TcbMirror &mir, const uint8_t *f, rxg_rec16 &r)
 {
     const TupleKey k = frame_key(f);
     uint8_t st = RXG_STATE_NONE;
     bool lhit = false;
-    const int32_t idx = c->mir.find(k.ports, k.dst, k.src, k.ports >> 16, &st, &lhit);
+    const int32_t idx = mir.find(k.ports, k.dst, k.src, k.ports >> 16, &st, &lhit);
     const bool missed = idx < 0 || lhit;  // pass 1 found nothing
-    const bool nslot = missed && c->mir.min_null < (lhit ? idx : c->mir.ntcb());
+    const bool nslot = missed && mir.min_null < (lhit ? idx : mir.ntcb());
     const uint8_t tflags = f[47];
     r.tcb_idx = idx;
     r.state = idx >= 0 ? st : (uint8_t)RXG_STATE_NONE;
@@ -419,45 +388,109 @@ static int reclassify(rxg_ctx *c, const std::vector<uint32_t> &sel, std::vector<
     return 0;
 }
 
-// A bulk change (a reload, a listener change, min_null moving) that leaves more than this
-// many packets of the burst stale re-classifies them in one GPU launch; fewer (and every
-// change to single tuples) are answered from the host index as each packet is reached.
-static constexpr uint32_t kHostReclassifyMax = 256;
+// One batch of table writes into the replay's log; with prebuilt ACKs handed out (ak_on), what
+// of it voids one (rxg_ack_take).
+static void absorb(rxg_ctx *c, bool ak_on, const WriteSet &w)
+{
+    if (ak_on) {
+        c->attached.ak_void_all |= w.all;
+        c->attached.ak_void_keys.insert(w.keys.begin(), w.keys.end());
+    }
+    c->replay.absorb(w);
+}
 
-// The side effects of etherin.c:21-35, ip.c:26-39 and tcp_in.c:47-72, in packet order.
+// The tracked writes since the last absorb; logged for the launch's later bursts, whose records
+// were computed before them too.
+static void absorb_touched(rxg_ctx *c, bool ak_on)
+{
+    c->launch_writes.add(c->touched);
+    absorb(c, ak_on, c->touched);
+    c->touched.clear();
+}
+
+// Packet j's record becomes r: the counter corrections, the TCBs whose prebuilt ACK that voids.
+static void refix(rxg_ctx *c, bool ak_on, uint32_t j, const rxg_rec16 &r, int64_t *delta)
+{
+    const rxg_rec16 &old = c->replay.record(j);
+    tcp_record_counters(old, -1, delta);
+    tcp_record_counters(r, +1, delta);
+    if (ak_on) {
+        c->attached.ak_void_tcb.insert(old.tcb_idx);
+        c->attached.ak_void_tcb.insert(r.tcb_idx);
+    }
+    c->replay.fixed(j, r);
+}
+
+// The side effects of etherin.c:21-35, ip.c:26-39 and tcp_in.c:47-72 for one packet.
+static void dispatch(rxg_ctx *c, const rxg_handoff_ops *ops, const rxg_rec16 &r, void *m, uint8_t *f)
+{
+    void *ip = f + RXG_OFF_IP, *tcp = f + RXG_OFF_TCP;
+    switch (r.verdict) {
+    case RXG_V_ARP:
+        if (ops->arp_in) ops->arp_in(ops->user, m);
+        if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
+        break;
+    case RXG_V_DROP_L2:
+    case RXG_V_DROP_NONTCP:
+        if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
+        break;
+    default: {
+        // ip.c:30-32 ARP learn on the host-order source address
+        const uint32_t src = ((uint32_t)f[26] << 24) | ((uint32_t)f[27] << 16) | ((uint32_t)f[28] << 8) | f[29];
+        if (c->arp_enabled) {
+            // the mirror answers get_mac: unknown at the burst and not added since
+            if ((r.flags & RXG_F_ARP_LEARN) && ops->add_mac && !c->arp_since_burst.count(src)) {
+                ops->add_mac(ops->user, src, f + 6);
+                rxg_arp_learned(c, src);  // idempotent if the caller's add_mac mirrors too
+            }
+        } else {
+            unsigned char mac[6];
+            if (ops->get_mac && ops->add_mac && ops->get_mac(ops->user, src, mac) == 0)
+                ops->add_mac(ops->user, src, f + 6);
+        }
+        if ((ops->flags & RXG_OPS_VERIFY_TCP_CKSUM) && !(r.flags & RXG_F_TCP_OK)) {
+            // tcp_in.c:37-40 with the check compiled in: free, ++tcpchecksumerror
+            if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
+            if (ops->tcpchecksumerror) ++*ops->tcpchecksumerror;
+        } else if (r.verdict == RXG_V_RST_NOPCB || r.verdict == RXG_V_RST_LISTEN_NONSYN) {
+            if (r.verdict == RXG_V_RST_NOPCB && ops->tcpnopcb) ++*ops->tcpnopcb;  // tcp_in.c:48
+            if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
+            if (ops->send_reset) ops->send_reset(ops->user, ip, tcp);
+        } else {  // RXG_V_DISPATCH
+            const uint32_t seq = ((uint32_t)f[38] << 24) | ((uint32_t)f[39] << 16) | ((uint32_t)f[40] << 8) | f[41];
+            const uint32_t ack = ((uint32_t)f[42] << 24) | ((uint32_t)f[43] << 16) | ((uint32_t)f[44] << 8) | f[45];
+            if (ops->on_segment) ops->on_segment(ops->user, r.tcb_idx, seq, ack);
+            if (ops->tcpswitch) ops->tcpswitch(ops->user, r.tcb_idx, r.state, tcp, ip, m);
+        }
+    }
+    }
+}
+
+// The burst's packets into the caller's handlers in packet order; a packet whose record a table
+// write made stale (rxg::ReplayLog, rxg_replaylog.h) is re-classified before its handlers run.
 extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const *mbufs,
                              void *const *frames, const void *recs, uint32_t n, uint32_t stride)
 {
     if (!c) return fail(-EINVAL, "rxg_rx_replay: NULL argument");
-    // on every way out: no packet is being replayed, and the resets attached for this replay
-    // (rxg_reset_attach) are no longer named
+    ReplayAttached &att = c->attached;
+    // on every way out: no packet is being replayed, and what was attached for this replay is no
+    // longer named
     struct PosGuard {
-        rxg_ctx *c;
+        ReplayAttached &a;
         bool done = false;  // the replay ran to its end
         ~PosGuard()
         {
             // prebuilt ACKs (rxg_acks_attach) are only handed out after a replay that saw the whole
             // burst: one that fails, in its argument checks or later, ends the attachment
-            if (!done) acks_detach(c);
-            c->replay_pos = -1;
-            c->rst_host = nullptr;
-            c->rst_idx = nullptr;
-            c->rst_n = c->rst_cur = 0;
-            c->opt_host = nullptr;
-            c->opt_n = 0;
-            c->opt_live = false;
-            c->fs_host = nullptr;
-            c->fs_m = 0;
-            c->ft_order = nullptr;
-            c->ft_trains = nullptr;
-            c->ft_nseg = c->ft_ntrains = 0;
+            if (!done) a.acks_detach();
+            a.end_of_replay();
         }
-    } pos_guard{c};
+    } pos_guard{att};
     // the prebuilt ACKs (rxg_acks_attach) outlive one replay: an attachment that has had its
     // replay ends here, a fresh one belongs to this burst (and ends with it if it fails: pos_guard)
-    if (c->ak_phase == 2u) acks_detach(c);
-    else if (c->ak_phase == 1u) c->ak_phase = 2u;
-    const bool ak_on = c->ak_phase == 2u;
+    if (att.ak_phase == 2u) att.acks_detach();
+    else if (att.ak_phase == 1u) att.ak_phase = 2u;
+    const bool ak_on = att.ak_phase == 2u;
     if (!ops || (n && (!mbufs || !frames || !recs)))
         return fail(-EINVAL, "rxg_rx_replay: NULL argument");
     if (!rec_kind_ok(stride)) return fail(-EINVAL, "rxg_rx_replay: stride %u", stride);
@@ -468,194 +501,35 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
     // the re-classify launches and the counter correction run on this context's device
     // (a group replays several contexts from one thread, rxg_group.cpp)
     if (int rc = set_device(c)) return rc;
-    c->opt_live = c->opt_host && c->opt_n == n;  // (rxg_rx_opts_attach) the copy is this burst's
-    std::vector<rxg_rec16> &cur = c->rp_cur;
-    cur.resize(n);
-    if (stride == RXG_REC8)
-        for (uint32_t i = 0; i < n; ++i) rxg_rec8_expand((const rxg_rec8 *)recs + i, &cur[i]);
-    else
-        for (uint32_t i = 0; i < n; ++i) cur[i] = *(const rxg_rec16 *)((const uint8_t *)recs + (size_t)i * stride);
-    int64_t delta[RXG_NCOUNTERS] = {0};
-
-    // Staleness by write sequence numbers, checked when a packet is reached (its header is
-    // read there anyway; no per-burst index).  Each batch of tracked writes (those of one
-    // handler call, or those made between the burst and the replay) gets a number; a record
-    // computed at number s is stale when a later write touched what it depends on: its tuple
-    // (pass 1, old or new tuple of a written slot), or -- for a packet pass 1 did not answer
-    // -- a LISTENING slot on its dport or the lowest NULL slot (pass 2); any write for a
-    // frame under 54 bytes; everything after a reload.
-    std::vector<uint32_t> &pkt_seq = c->rp_seq;
-    pkt_seq.assign(n, 0u);  // 0 = as the burst classified it
-    uint32_t wseq = 0, any_seq = 0, all_seq = 0, minnull_seq = 0, bulk_seq = 0, scanned_seq = 0;
-    std::unordered_map<TupleKey, uint32_t, TupleKeyHash> key_seq;
-    std::vector<std::pair<int32_t, uint32_t>> listen_seq;  // (dport, seq): rare
-    std::vector<uint64_t> &filt = c->rp_filter;            // 65 536-bit filter of written tuples
-    bool filt_used = false;
-    auto absorb_lists = [&](const std::vector<TupleKey> &keys, const std::vector<int32_t> &listen, bool all,
-                            bool pass2) {
-        ++wseq;
-        any_seq = wseq;
-        if (ak_on) {  // what voids a prebuilt ACK (rxg_ack_take)
-            c->ak_void_all |= all;
-            c->ak_void_keys.insert(keys.begin(), keys.end());
-        }
-        if (all) all_seq = bulk_seq = wseq;
-        if (pass2) minnull_seq = bulk_seq = wseq;
-        for (const TupleKey &k : keys) {
-            key_seq[k] = wseq;
-            const uint32_t h = filter_hash(k);
-            if (!filt_used) {
-                filt.assign(1024, 0ull);
-                filt_used = true;
-            }
-            filt[(h >> 6) & 1023u] |= 1ull << (h & 63u);
-        }
-        for (int32_t d : listen) {
-            bool found = false;
-            for (auto &e : listen_seq)
-                if (e.first == d) {
-                    e.second = wseq;
-                    found = true;
-                }
-            if (!found) listen_seq.emplace_back(d, wseq);
-            bulk_seq = wseq;
-        }
-    };
-    // the tracked writes since the last absorb; logged for the launch's later bursts, whose
-    // records were computed before them too
-    auto absorb = [&]() {
-        c->launch_keys.insert(c->launch_keys.end(), c->touched_keys.begin(), c->touched_keys.end());
-        c->launch_listen.insert(c->launch_listen.end(), c->touched_listen.begin(), c->touched_listen.end());
-        c->launch_all |= c->touched_all;
-        c->launch_pass2 |= c->touched_pass2;
-        absorb_lists(c->touched_keys, c->touched_listen, c->touched_all, c->touched_pass2);
-        c->touched_keys.clear();
-        c->touched_listen.clear();
-        c->touched_all = c->touched_pass2 = false;
-    };
-    auto stale = [&](uint32_t j) -> bool {
-        const rxg_rec16 &q = cur[j];
-        const uint32_t s = pkt_seq[j];
-        if (any_seq <= s || !rec_is_tcp(q)) return false;
-        if (all_seq > s || (q.flags & RXG_F_TRUNC)) return true;
-        const TupleKey k = frame_key((const uint8_t *)frames[j]);
-        if (filt_used) {
-            const uint32_t h = filter_hash(k);
-            if ((filt[(h >> 6) & 1023u] >> (h & 63u)) & 1ull) {
-                auto it = key_seq.find(k);
-                if (it != key_seq.end() && it->second > s) return true;
-            }
-        }
-        const int32_t d = (int32_t)(k.ports >> 16);
-        if (rec_pass2(q)) {
-            if (minnull_seq > s) return true;
-            for (const auto &e : listen_seq)
-                if (e.first == d && e.second > s) return true;
-        }
-        return false;
-    };
+    att.opt_live = att.opt_host && att.opt_n == n;  // (rxg_rx_opts_attach) the copy is this burst's
+    ReplayLog &log = c->replay;
+    log.begin(n, recs, stride);
     // writes the replays of this launch's earlier bursts made, then those since
-    if (c->replay_cursor > 0 &&
-        (!c->launch_keys.empty() || !c->launch_listen.empty() || c->launch_all || c->launch_pass2))
-        absorb_lists(c->launch_keys, c->launch_listen, c->launch_all, c->launch_pass2);
-    if (!c->touched_keys.empty() || !c->touched_listen.empty() || c->touched_all || c->touched_pass2) absorb();
+    if (c->replay_cursor > 0 && !c->launch_writes.empty()) absorb(c, ak_on, c->launch_writes);
+    if (!c->touched.empty()) absorb_touched(c, ak_on);
 
+    int64_t delta[RXG_NCOUNTERS] = {0};
     std::vector<uint32_t> sel;
     std::vector<rxg_rec16> fix;
     for (uint32_t i = 0; i < n; ++i) {
-        if (any_seq > pkt_seq[i] && stale(i)) {
-            ++c->rp_stats[0];
-            const bool trunc = (cur[i].flags & RXG_F_TRUNC) != 0;
-            bool batched = false;
-            if (c->replay_on_device || trunc || bulk_seq > scanned_seq) {
-                // what is stale from here on: one GPU launch if the set is large (a bulk
-                // change), or always on the device path / for a short frame
-                sel.clear();
-                for (uint32_t j = i; j < n; ++j)
-                    if (stale(j)) sel.push_back(j);
-                scanned_seq = wseq;
-                if (c->replay_on_device || trunc || sel.size() > kHostReclassifyMax) {
-                    int rc = reclassify(c, sel, fix);
-                    if (rc) return rc;
-                    for (size_t k = 0; k < sel.size(); ++k) {
-                        tcp_record_counters(cur[sel[k]], -1, delta);
-                        tcp_record_counters(fix[k], +1, delta);
-                        if (ak_on) {
-                            c->ak_void_tcb.insert(cur[sel[k]].tcb_idx);
-                            c->ak_void_tcb.insert(fix[k].tcb_idx);
-                        }
-                        cur[sel[k]] = fix[k];
-                        pkt_seq[sel[k]] = wseq;
-                    }
-                    c->rp_stats[2] += sel.size();
-                    ++c->rp_stats[3];
-                    batched = true;
-                }
-            }
-            if (!batched) {
-                if (c->mir.need_rebuild) {  // a reload / growth inside the replay: index first
-                    int rc = tcb_push(c);
-                    if (rc) return rc;
-                }
-                rxg_rec16 r = cur[i];
-                host_classify(c, (const uint8_t *)frames[i], r);
-                tcp_record_counters(cur[i], -1, delta);
-                tcp_record_counters(r, +1, delta);
-                if (ak_on) {
-                    c->ak_void_tcb.insert(cur[i].tcb_idx);
-                    c->ak_void_tcb.insert(r.tcb_idx);
-                }
-                cur[i] = r;
-                pkt_seq[i] = wseq;
-                ++c->rp_stats[1];
-            }
-        }
-        const rxg_rec16 &r = cur[i];
-        c->replay_pos = i;  // rxg_payload_take answers for this packet
-        void *m = mbufs[i];
-        uint8_t *f = (uint8_t *)frames[i];
-        void *ip = f + RXG_OFF_IP, *tcp = f + RXG_OFF_TCP;
-        const uint64_t gen_before = c->gen;
-        switch (r.verdict) {
-        case RXG_V_ARP:
-            if (ops->arp_in) ops->arp_in(ops->user, m);
-            if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
-            break;
-        case RXG_V_DROP_L2:
-        case RXG_V_DROP_NONTCP:
-            if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
-            break;
-        default: {
-            // ip.c:30-32 ARP learn on the host-order source address
-            const uint32_t src = ((uint32_t)f[26] << 24) | ((uint32_t)f[27] << 16) | ((uint32_t)f[28] << 8) | f[29];
-            if (c->arp_enabled) {
-                // the mirror answers get_mac: unknown at the burst and not added since
-                if ((r.flags & RXG_F_ARP_LEARN) && ops->add_mac && !c->arp_since_burst.count(src)) {
-                    ops->add_mac(ops->user, src, f + 6);
-                    rxg_arp_learned(c, src);  // idempotent if the caller's add_mac mirrors too
-                }
+        if (log.stale(i, frames)) {
+            const ReplayLog::Plan p = log.plan(i, frames, n, c->replay_on_device, sel);
+            if (p == ReplayLog::kLaunch) {
+                if (int rc = reclassify(c, sel, fix)) return rc;
+                for (size_t k = 0; k < sel.size(); ++k) refix(c, ak_on, sel[k], fix[k], delta);
             } else {
-                unsigned char mac[6];
-                if (ops->get_mac && ops->add_mac && ops->get_mac(ops->user, src, mac) == 0)
-                    ops->add_mac(ops->user, src, f + 6);
+                if (c->mir.need_rebuild)  // a reload / growth inside the replay: index first
+                    if (int rc = tcb_push(c)) return rc;
+                rxg_rec16 r = log.record(i);
+                host_classify(c->mir, (const uint8_t *)frames[i], r);
+                refix(c, ak_on, i, r, delta);
             }
-            if ((ops->flags & RXG_OPS_VERIFY_TCP_CKSUM) && !(r.flags & RXG_F_TCP_OK)) {
-                // tcp_in.c:37-40 with the check compiled in: free, ++tcpchecksumerror
-                if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
-                if (ops->tcpchecksumerror) ++*ops->tcpchecksumerror;
-            } else if (r.verdict == RXG_V_RST_NOPCB || r.verdict == RXG_V_RST_LISTEN_NONSYN) {
-                if (r.verdict == RXG_V_RST_NOPCB && ops->tcpnopcb) ++*ops->tcpnopcb;  // tcp_in.c:48
-                if (ops->free_mbuf) ops->free_mbuf(ops->user, m);
-                if (ops->send_reset) ops->send_reset(ops->user, ip, tcp);
-            } else {  // RXG_V_DISPATCH
-                const uint32_t seq = ((uint32_t)f[38] << 24) | ((uint32_t)f[39] << 16) | ((uint32_t)f[40] << 8) | f[41];
-                const uint32_t ack = ((uint32_t)f[42] << 24) | ((uint32_t)f[43] << 16) | ((uint32_t)f[44] << 8) | f[45];
-                if (ops->on_segment) ops->on_segment(ops->user, r.tcb_idx, seq, ack);
-                if (ops->tcpswitch) ops->tcpswitch(ops->user, r.tcb_idx, r.state, tcp, ip, m);
-            }
+            log.done(p, sel.size());
         }
-        }
-        if (c->gen != gen_before) absorb();  // the handlers changed the table
+        att.pos = i;  // rxg_payload_take answers for this packet
+        const uint64_t gen_before = c->gen;
+        dispatch(c, ops, log.record(i), mbufs[i], (uint8_t *)frames[i]);
+        if (c->gen != gen_before) absorb_touched(c, ak_on);  // the handlers changed the table
     }
     // the launch's next burst is replayed next (a single burst can be replayed again)
     if (c->replay_cursor + 1 < c->last_bursts.size()) select_burst(c, c->replay_cursor + 1);
@@ -672,6 +546,6 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
 extern "C" int rxg_replay_stats(rxg_ctx *c, uint64_t out[4])
 {
     if (!c || !out) return fail(-EINVAL, "rxg_replay_stats: NULL argument");
-    for (int k = 0; k < 4; ++k) out[k] = c->rp_stats[k];
+    for (int k = 0; k < 4; ++k) out[k] = c->replay.stats[k];
     return 0;
 }

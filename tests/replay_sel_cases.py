@@ -15,25 +15,27 @@ wrong tcb_idx.  Pass-2 packets come from client i mod 60, whom no row names.
 
 Writers.  A writer is a flow frame whose tcpswitch handler makes one write (apply_writer, on the
 python rows and, with an engine, through rxg_tcb_*): `reload` loads the table rotated by one slot
-(every index moves; touched_all), `listener` removes the 8080 listener, or appends it again
-(touched_listen), `minnull` removes the lowest spare row, which lies below the NULL slot and below
-the port-80 listener (touched_pass2), `tuple` upserts one flow's slot with the same tuple in
-SYN_RECV, or back in ESTABLISHED (touched_keys).  No other handler writes.
+(every index moves; touched.all), `listener` removes the 8080 listener, or appends it again
+(touched.listen), `minnull` removes the lowest spare row, which lies below the NULL slot and below
+the port-80 listener (touched.pass2), `tuple` upserts one flow's slot with the same tuple in
+SYN_RECV, or back in ESTABLISHED (touched.keys).  No other handler writes.
 
 Expectation.  Frame i belongs to the epoch of the writers before it; Case.expect runs
 oracle.rx_batch over each epoch's frames against that epoch's rows and sums the counters.
 
-Model.  Case.sim restates rxg_rx_replay's rule (stale(), absorb, bulk_seq / scanned_seq,
-kHostReclassifyMax, the forced launch for F_TRUNC, pkt_seq after a fix-up, launch_* across the
-bursts of a launch) over the classification of every frame against every epoch's rows, for a
-default and a RXG_CFG_REPLAY_ON_DEVICE context, and gives every launch's list and the four
-rxg_replay_stats figures.  Table restates which touched_* a write sets (rxg_host.cpp note_slot,
-rxg_tcb_upsert / _remove / _load; TcbMirror's min_null and need_rebuild).  slices_of, blocks_of,
-flushes and lookaheads derive the launch's dealing from a list as multiburst_cases does for a
-burst (RS = 11 slots of 1 KiB for REC16, 4 for the all-small scratch, 6 for the class path's).
+Model.  Case.sim restates rxg_rx_replay's rule (rxg::ReplayLog, csrc/rxg_replaylog.h: stale(),
+absorb(), plan() with bulk_seq / scanned_seq, kHostReclassifyMax and the forced launch for F_TRUNC,
+pkt_seq after fixed(); rxg_ctx::launch_writes across the bursts of a launch) over the classification
+of every frame against every epoch's rows, for a default and a RXG_CFG_REPLAY_ON_DEVICE context, and
+gives every launch's list, the four rxg_replay_stats figures and every writer's Touch.  Table
+restates what a write adds to rxg_ctx::touched (rxg_host.cpp note_slot, rxg_tcb_upsert / _remove /
+_load; TcbMirror's min_null and need_rebuild).  slices_of, blocks_of, flushes and lookaheads derive
+the launch's dealing from a list as multiburst_cases does for a burst (RS = 11 slots of 1 KiB for
+REC16, 4 for the all-small scratch, 6 for the class path's).
 
 tests/test_replay_sel_cases_host.py holds every claim against the sets and the model;
-tests/test_gpu_replay_sel_edges.py runs them."""
+tests/test_replaylog_host.py runs the model against the real ReplayLog on the CPU;
+tests/test_gpu_replay_sel_edges.py runs the sets on the GPU."""
 from __future__ import annotations
 
 import functools
@@ -50,7 +52,7 @@ RS16 = 11                      # rxg_rx.h rx_body: RS for REC16
 SLOT16 = 1024                  # ring_slot_u4(16) * 16
 SMALL_SCRATCH = 4096           # small_step: ring.scratch(.., 4096, ..)
 CLASS_SCRATCH = 6 * 256 + 4096  # rx_body: NF16 * 256 + 4096
-K_HOST_MAX = 256               # rxg_replay.cpp kHostReclassifyMax
+K_HOST_MAX = 256               # rxg_replaylog.h kHostReclassifyMax
 FILL = 0xA5
 POOL_TAIL = 16384              # fill behind the last frame of every device pool
 LISTENING, SYN_RECV, ESTABLISHED = 1, 3, 4
@@ -127,14 +129,14 @@ def key_of_row(r):
 
 
 def key_of_frame(f: bytes):
-    """rxg_replay.cpp frame_key (frames of >= 54 bytes)."""
+    """rxg_replaylog.h frame_key (frames of >= 54 bytes)."""
     return ((int.from_bytes(f[36:38], "big") << 16) | int.from_bytes(f[34:36], "big"),
             int.from_bytes(f[30:34], "little"), int.from_bytes(f[26:30], "big"))
 
 
 # ------------------------------------------------------------------------- the table's writes ---
 class Touch:
-    """What one handler call's writes leave in rxg_ctx::touched_*."""
+    """What one handler call's writes leave in rxg_ctx::touched (rxg::WriteSet)."""
 
     def __init__(self, keys=(), listen=(), all_=False, pass2=False):
         self.keys, self.listen, self.all, self.pass2 = list(keys), list(listen), all_, pass2
@@ -150,8 +152,8 @@ class Touch:
 
 
 class Table:
-    """tcbs[] as python rows, and which touched_* every write sets.  need_rebuild: a load has not
-    been pushed yet (every write then sets touched_pass2); a fix-up pushes (pushed())."""
+    """tcbs[] as python rows, and what every write adds to touched.  need_rebuild: a load has not
+    been pushed yet (every write then sets touched.pass2); a fix-up pushes (pushed())."""
 
     def __init__(self, rows):
         self.rows, self.need_rebuild = list(rows), False
@@ -285,6 +287,7 @@ class Sim:
         self.launches = []       # (burst, list of frame indices within the burst)
         self.marked = self.host = self.dev = 0
         self.seen = []           # per frame the epoch whose classification its handler saw
+        self.touches = []        # (writer frame, the Touch its write left), in frame order
 
     @property
     def stats(self):
@@ -382,7 +385,7 @@ class Case:
         keys = [key_of_frame(f) if len(f) >= 54 else None for f in self.frames]
         cur = [0] * self.n           # the epoch whose classification frame j's record holds
         table, e = Table(ROWS), 0
-        launch = Touch()             # rxg_ctx::launch_*: the writes of this launch's replays so far
+        launch = Touch()             # rxg_ctx::launch_writes: the writes of this launch's replays so far
 
         def pass2(j):
             r = self.cls(cur[j])[j]
@@ -444,6 +447,7 @@ class Case:
                     t = apply_writer(table, self.writers[i])
                     e += 1
                     assert table.rows == self.epochs[e][0]
+                    out.touches.append((i, t))
                     launch.add(t)
                     absorb_lists(t)
         return out
@@ -562,7 +566,7 @@ def _build(name: str) -> Case:
         w = rewrites_writers("a", REWRITES_N)
         sp = rewrites_specs(REWRITES_N, w)
         bursts = None
-        if form in ("multi", "smulti"):     # bursts 1 and 2 carry no writer: re-selected whole (launch_all)
+        if form in ("multi", "smulti"):     # bursts 1 and 2 carry no writer: re-selected whole (launch_writes.all)
             sp = sp + rewrites_specs(365, {})
             bursts = [(0, REWRITES_N), (REWRITES_N, REWRITES_N + 300), (REWRITES_N + 300, REWRITES_N + 365)]
         return Case(name, sp, w, bursts=bursts, form=form, order="shuffle" if form == "dev" else "fwd", kind=kind)

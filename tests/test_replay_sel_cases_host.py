@@ -72,7 +72,7 @@ def test_writers_touch_what_they_claim():
     w = rc.apply_writer(t, "reload")
     assert w.all and not (w.keys or w.listen or w.pass2) and t.need_rebuild
     assert t.rows == [rc.ROWS[1], rc.L80, None] + rc.ROWS[4:261] + [None, rc.L8080, None]
-    # a write while the load is pending sets touched_pass2 (rxg_tcb_upsert: mir.need_rebuild)
+    # a write while the load is pending sets touched.pass2 (rxg_tcb_upsert: mir.need_rebuild)
     assert rc.apply_writer(t, ("tuple", 5)).pass2
     t.pushed()
     assert not rc.apply_writer(t, ("tuple", 5)).pass2
@@ -380,7 +380,7 @@ def test_forms_and_checks():
             if f in ("multi", "smulti"):
                 assert c.bursts == [(0, 1200), (1200, 1500), (1500, 1565)] and max(c.writers) < 1200
                 d, v = c.sim(False), c.sim(True)
-                # bursts 1 and 2 re-selected whole through launch_all: a launch and 65 host fix-ups
+                # bursts 1 and 2 re-selected whole through launch_writes.all: a launch and 65 host fix-ups
                 assert v.launches[3:] == [(1, list(range(300))), (2, list(range(65)))]
                 assert d.launches[2:] == [(1, list(range(300)))] and d.stats["host_fixups"] == 1 + 65
             else:
