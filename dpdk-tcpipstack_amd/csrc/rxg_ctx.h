@@ -9,7 +9,9 @@
 //                   read them (patch ring, carried list, mirror_ev, reader events): HIP-free
 //   rxg_server.cpp  latency mode (the persistent server kernel) and host-buffer bursts
 //   rxg_replay.cpp  the per-packet replay into the caller's handlers, the payload hand-off,
-//                   what a replay hands out (ReplayAttached below), ether_in
+//                   the C entry points of what a replay hands out, ether_in
+//   rxg_attached.h  what a replay hands out and the rules it is answered by (ReplayAttached),
+//                   the receive-window mirror (RcvWindow): HIP-free
 //   rxg_replaylog.h which packets a table write made stale and how each is fixed (WriteSet,
 //                   ReplayLog): HIP-free
 //   rxg_util.cpp    synthetic frames, memory and event helpers
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "rxg.h"
+#include "rxg_attached.h"
 #include "rxg_common.h"
 #include "rxg_kernels.h"
 #include "rxg_mirror.h"
@@ -148,67 +151,6 @@ struct SerialScratch {
 enum GridOp { kGridPay, kGridTxBuild, kGridTxBuildOpt, kGridTxReset, kGridRxOpts, kGridTxPlan, kGridFlowSum, kGridFlowTrain,
               kGridTrainPay, kGridAckPlan, kGridOps };
 
-// What a replay hands out to the handlers it calls: host copies the caller attached for the
-// replay that follows, answered for the packet being replayed (pos).
-struct ReplayAttached {
-    int64_t pos = -1;  // packet whose handlers rxg_rx_replay is running
-    // rxg_reset_attach: a call's resets and their packet indices, and rxg_reset_take's cursor
-    uint8_t *rst_host = nullptr;
-    const uint32_t *rst_idx = nullptr;
-    uint64_t rst_n = 0, rst_cur = 0;
-    // rxg_rx_opts_attach: a rxg_rx_opts_dev call's records; rxg_rx_opt_current answers from them
-    const rxg_rx_opt *opt_host = nullptr;
-    uint32_t opt_n = 0;
-    bool opt_live = false;  // the running replay's burst has opt_n frames
-    // rxg_flow_sums_attach: a call's summaries; rxg_flow_sum_current answers from them
-    const rxg_flow_sum *fs_host = nullptr;
-    uint64_t fs_m = 0;
-    // rxg_flow_trains_attach: a call's order and trains; rxg_flow_train_current answers from them
-    const uint32_t *ft_order = nullptr;
-    const rxg_flow_train *ft_trains = nullptr;
-    uint64_t ft_nseg = 0, ft_ntrains = 0;
-    // rxg_acks_attach: a call's acks and the frames built from its segs.  ak_phase 1: attached,
-    // waiting for its replay; 2: that replay has begun (rxg_ack_take answers, also after it
-    // returned); the next replay, attach or fini ends it.  What the replay saw that voids a
-    // prebuilt ACK: the TCBs a re-classification took a packet from or gave one to, the tuples of
-    // written slots (the replay's own write log), a whole-table change
-    const rxg_ack *ak_acks = nullptr;
-    uint8_t *ak_frames = nullptr;
-    uint64_t ak_n = 0;
-    uint32_t ak_stride = 0, ak_phase = 0;
-    std::unordered_set<int32_t> ak_void_tcb;
-    std::unordered_set<rxg::TupleKey, rxg::TupleKeyHash> ak_void_keys;
-    bool ak_void_all = false;
-
-    // no packet is being replayed, and what was attached for this replay is no longer named
-    // (the ACKs outlive it: acks_detach)
-    void end_of_replay()
-    {
-        pos = -1;
-        rst_host = nullptr;
-        rst_idx = nullptr;
-        rst_n = rst_cur = 0;
-        opt_host = nullptr;
-        opt_n = 0;
-        opt_live = false;
-        fs_host = nullptr;
-        fs_m = 0;
-        ft_order = nullptr;
-        ft_trains = nullptr;
-        ft_nseg = ft_ntrains = 0;
-    }
-    void acks_detach()
-    {
-        ak_acks = nullptr;
-        ak_frames = nullptr;
-        ak_n = 0;
-        ak_stride = ak_phase = 0;
-        ak_void_tcb.clear();
-        ak_void_keys.clear();
-        ak_void_all = false;
-    }
-};
-
 struct rxg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -271,19 +213,24 @@ struct rxg_ctx {
     uint32_t last_stride = 0;
     DevBuf d_sel, d_fix;
 
-    // payload hand-off: receive-window mirror (0 unknown, 1 no pairs, 2 pairs pending) and
-    // the gathered burst's message descriptors (pinned host copy)
-    std::vector<uint32_t> rcv_cur;
-    std::vector<uint8_t> rcv_state;
+    // payload hand-off: the receive-window mirror (rxg_rcv_set), the gathers' look-back words
+    rxg::RcvWindow rcv;
     DevBuf d_pg_status, d_pg_ticket;
     unsigned long long pg_tickets = 0;  // workgroups the gathers have launched so far
     uint32_t pg_epoch = 0;
-    rxg_payload_msg *h_pm = nullptr;
-    const rxg_payload_msg *d_pm = nullptr;  // the gather's descriptors (device)
-    uint32_t h_pm_cap = 0, pm_n = 0;
-    bool pm_pending = false;  // h_pm not fetched yet for this gather
-    hipEvent_t pm_ev = nullptr;
-    ReplayAttached attached;  // what the replay hands out, and the packet it is at
+    // The messages rxg_payload_take answers from: those of the last gather, train payload or fused
+    // burst (pm_handoff records where they are), fetched into a pinned host copy at the first take.
+    struct PayloadMsgs {
+        const rxg_payload_msg *dev = nullptr;  // the call's descriptors (device)
+        const uint64_t *used = nullptr;        // its arena_used (device); NULL: no look-back to time out
+        uint32_t n = 0;                        // 0: the selected burst has none
+        hipEvent_t ev = nullptr;               // recorded after the call's last launch
+        bool pending = false;                  // host not fetched yet for this call
+        bool poisoned = false;                 // its look-back timed out: no payload is handed out
+        rxg_payload_msg *host = nullptr;       // pinned, host_cap entries
+        uint32_t host_cap = 0;
+    } pm;
+    rxg::ReplayAttached attached;  // what the replay hands out, and the packet it is at
 
     // rxg_tx_reset_dev: the slice counts its three launches share (buf[0])
     SerialScratch rst{"rxg_tx_reset_dev"};
@@ -309,9 +256,6 @@ struct rxg_ctx {
     bool arp_enabled = false;
     rxg::ArpMirror arp;
     std::unordered_map<uint32_t, int> arp_since_burst;  // learned after the last burst
-
-    const uint64_t *pm_used = nullptr;  // the gather's arena_used (device)
-    bool pm_poisoned = false;           // that gather timed out: no payload is handed out
 
     // host-buffer burst staging
     uint32_t max_batch = 0;
@@ -418,6 +362,9 @@ void select_burst(rxg_ctx *c, uint32_t j);
 int begin_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bursts, uint32_t k, uint32_t rec_kind,
                  const char *who, uint32_t stride64 = 0, bool carry = false);
 int burst_offsets(rxg_ctx *c, hipStream_t st, const uint32_t **out);
+// The n messages at msgs (device), written by what was just launched on st, are what
+// rxg_payload_take answers from next; used: that call's arena_used (device), or NULL.
+int pm_handoff(rxg_ctx *c, hipStream_t st, const rxg_payload_msg *msgs, const uint64_t *used, uint32_t n);
 // the pending counter corrections (rxg_ctx::pend_delta) to the device, on c->stream
 int flush_delta(rxg_ctx *c);
 

@@ -181,8 +181,8 @@ extern "C" int rxg_fini(rxg_ctx *c)
                       &c->d_pg_ticket, &c->d_soff})
         if (b->p) (void)hipFree(b->p);
     for (SerialScratch *s : {&c->rst, &c->txp, &c->fs, &c->ft, &c->tp, &c->ak}) s->destroy();
-    if (c->h_pm) (void)hipHostFree(c->h_pm);
-    if (c->pm_ev) (void)hipEventDestroy(c->pm_ev);
+    if (c->pm.host) (void)hipHostFree(c->pm.host);
+    if (c->pm.ev) (void)hipEventDestroy(c->pm.ev);
     c->tables.destroy();
     if (c->counters) (void)hipFree(c->counters);
     if (c->h_arena) (void)hipHostFree(c->h_arena);
@@ -247,7 +247,7 @@ extern "C" int rxg_tcb_remove(rxg_ctx *c, int32_t idx)
     note_slot(c, idx);
     c->mir.remove(idx);
     if (c->mir.need_rebuild || c->mir.min_null != min_null) c->touched.pass2 = true;
-    if ((size_t)idx < c->rcv_state.size()) c->rcv_state[idx] = 0;  // FreeWindow
+    c->rcv.forget(idx);  // FreeWindow
     c->tables.tcb_changed();
     c->gen++;
     return 0;
@@ -278,8 +278,7 @@ extern "C" int rxg_tcb_load(rxg_ctx *c, const rxg_tcb_tuple *tcbs, const uint8_t
     c->tables.tcb_changed();
     c->touched.all = true;
     c->gen++;
-    c->rcv_cur.clear();
-    c->rcv_state.clear();
+    c->rcv.clear();
     return 0;
 }
 
@@ -489,7 +488,20 @@ void select_burst(rxg_ctx *c, uint32_t j)
     c->last_len = b.len;
     c->last_n = b.n;
     c->last_recs = b.recs;
-    c->pm_n = 0;  // a gather describes the burst it followed
+    c->pm.n = 0;  // a gather describes the burst it followed
+}
+
+int pm_handoff(rxg_ctx *c, hipStream_t st, const rxg_payload_msg *msgs, const uint64_t *used, uint32_t n)
+{
+    rxg_ctx::PayloadMsgs &pm = c->pm;
+    if (!pm.ev) HIP_OK(hipEventCreateWithFlags(&pm.ev, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(pm.ev, st));
+    pm.dev = msgs;
+    pm.used = used;
+    pm.n = n;
+    pm.pending = true;  // rxg_payload_take fetches them on its first call after this one
+    pm.poisoned = false;
+    return 0;
 }
 
 // Validation, mirror sync and the replay bookkeeping of a burst set (launched or served).
@@ -595,16 +607,8 @@ static int launch_bursts(rxg_ctx *c, const void *frames, const rxg_dev_burst *bu
     }
     if ((rc = c->tables.after(st))) return rc;
     c->burst_ok = true;
-    if (pay && k == 1 && bursts[0].n) {
-        // rxg_payload_take answers from this burst's messages (fetched at its first call)
-        if (!c->pm_ev) HIP_OK(hipEventCreateWithFlags(&c->pm_ev, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(c->pm_ev, st));
-        c->d_pm = pay->msgs;
-        c->pm_used = nullptr;  // no look-back: never poisoned
-        c->pm_n = bursts[0].n;
-        c->pm_pending = true;
-        c->pm_poisoned = false;
-    }
+    // rxg_payload_take answers from this burst's messages (no look-back: never poisoned)
+    if (pay && k == 1 && bursts[0].n) return pm_handoff(c, st, pay->msgs, nullptr, bursts[0].n);
     return 0;
 }
 

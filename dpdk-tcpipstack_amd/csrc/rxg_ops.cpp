@@ -342,7 +342,7 @@ extern "C" int rxg_train_payload_dev(rxg_ctx *c, const rxg_dev_train_payload *b,
     L.max_blocks = grid_cap(c, c->op_grid[kGridTrainPay]);
     // one gather or train payload in flight per context (rxg_payload_gather_dev's rule): the
     // messages rxg_payload_take reads are the last such call's
-    if (b->msgs && c->pm_ev) HIP_OK(hipStreamWaitEvent(st, c->pm_ev, 0));
+    if (b->msgs && c->pm.ev) HIP_OK(hipStreamWaitEvent(st, c->pm.ev, 0));
     if (b->n) {
         DevBuf &scratch = c->tp.buf[0];
         if ((rc = c->tp.grow(scratch, train_pay_scratch_bytes(b->n, b->cap_trains), false, st))) return rc;
@@ -350,16 +350,7 @@ extern "C" int rxg_train_payload_dev(rxg_ctx *c, const rxg_dev_train_payload *b,
         L.scratch = scratch.p;
     }
     if ((rc = c->tp.end(st, launch_train_pay(L, st)))) return rc;
-    if (b->msgs) {  // rxg_payload_take fetches the descriptors on its first call after this one
-        if (!c->pm_ev) HIP_OK(hipEventCreateWithFlags(&c->pm_ev, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(c->pm_ev, st));
-        c->d_pm = b->msgs;
-        c->pm_used = b->arena_used;
-        c->pm_n = b->n;
-        c->pm_pending = true;
-        c->pm_poisoned = false;
-    }
-    return 0;
+    return b->msgs ? pm_handoff(c, st, b->msgs, b->arena_used, b->n) : 0;
 }
 
 static_assert(sizeof(rxg_ack_state) == 16 && sizeof(rxg_ack) == 16 && sizeof(rxg_dev_ack_plan) == 128,

@@ -1,9 +1,8 @@
 // rxg_replay.cpp — the per-packet replay of a classified burst into the caller's handlers
 // (rxg_rx_replay: the reference's ether_in -> ip_in -> tcp_in order, re-classifying what a
 // handler's table write changed), the payload hand-off (rxg_payload_gather_dev, rxg_rcv_set,
-// rxg_payload_take), the prebuilt resets' hand-out (rxg_reset_attach, rxg_reset_take), the
-// parsed options' (rxg_rx_opts_attach, rxg_rx_opt_current), the prebuilt ACKs' (rxg_acks_attach,
-// rxg_ack_take) and the one-frame rxg_ether_in.
+// rxg_payload_take), the C entry points of what a replay hands out (resets, options, flow
+// summaries, flow trains, ACKs: their rules are rxg_attached.h's) and the one-frame rxg_ether_in.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -56,7 +55,7 @@ extern "C" int rxg_payload_gather_dev(rxg_ctx *c, const rxg_payload_out *o, void
     }
     // one gather in flight per context: the ticket counter and the status words are shared,
     // so a gather on another stream waits for the previous one
-    if (c->pm_ev) HIP_OK(hipStreamWaitEvent(st, c->pm_ev, 0));
+    if (c->pm.ev) HIP_OK(hipStreamWaitEvent(st, c->pm.ev, 0));
     c->pg_epoch = (c->pg_epoch % ((1u << 30) - 1u)) + 1u;
     LaunchPayload P;
     P.frames = c->last_frames;
@@ -76,249 +75,151 @@ extern "C" int rxg_payload_gather_dev(rxg_ctx *c, const rxg_payload_out *o, void
     uint32_t tickets = 0;
     HIP_OK(launch_payload(P, st, &tickets));
     c->pg_tickets += tickets;
-    // rxg_payload_take fetches the descriptors on its first call after this gather
-    if (!c->pm_ev) HIP_OK(hipEventCreateWithFlags(&c->pm_ev, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(c->pm_ev, st));
-    c->d_pm = o->msgs;
-    c->pm_used = o->arena_used;
-    c->pm_n = n;
-    c->pm_pending = true;
-    c->pm_poisoned = false;
-    return 0;
+    return pm_handoff(c, st, o->msgs, o->arena_used, n);
 }
 
 extern "C" int rxg_rcv_set(rxg_ctx *c, int32_t idx, uint32_t cur_seq, uint32_t pairs_pending)
 {
     if (!c) return fail(-EINVAL, "rxg_rcv_set: ctx NULL");
     if (idx < 0 || idx >= kMaxTcbs) return fail(-EINVAL, "rxg_rcv_set: index %d", idx);
-    if ((size_t)idx >= c->rcv_state.size()) {
-        c->rcv_state.resize((size_t)idx + 1, 0);
-        c->rcv_cur.resize((size_t)idx + 1, 0);
-    }
-    c->rcv_cur[idx] = cur_seq;
-    c->rcv_state[idx] = pairs_pending ? 2 : 1;
+    c->rcv.set(idx, cur_seq, pairs_pending != 0);
     return 0;
 }
 
-// PushData (tcp_windows.c:341-358) with an empty SeqPairs list and
-// CurrentSequenceNumber == seq: the out-of-window test needs SeqPairs (:345) and is
-// skipped; the duplicate test (:349) drops iff cur > seq + Length (u32); AdjustPair puts
-// the one pair at the head (:42-110, returns seq + Length + FIN); GetData pops it with
-// offset 0 and copies Length bytes (:158-180) -> one message of exactly this payload.
+// The messages of the last gather into the pinned host copy, and whether its look-back timed out.
+static int pm_fetch(rxg_ctx *c)
+{
+    rxg_ctx::PayloadMsgs &pm = c->pm;
+    if (int rc = set_device(c)) return rc;
+    HIP_OK(hipEventSynchronize(pm.ev));
+    if (pm.n > pm.host_cap) {
+        if (pm.host) HIP_OK(hipHostFree(pm.host));
+        pm.host = nullptr;
+        pm.host_cap = 0;
+        HIP_OK(hipHostMalloc((void **)&pm.host, (size_t)pm.n * sizeof(rxg_payload_msg), hipHostMallocDefault));
+        pm.host_cap = pm.n;
+    }
+    uint64_t used = 0;
+    HIP_OK(hipMemcpyAsync(pm.host, pm.dev, (size_t)pm.n * sizeof(rxg_payload_msg), hipMemcpyDeviceToHost, c->stream));
+    if (pm.used)  // (a fused burst, rxg_rx_burst_payload_dev, has no look-back to time out)
+        HIP_OK(hipMemcpyAsync(&used, pm.used, sizeof used, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    pm.pending = false;
+    // a gather whose look-back timed out (arena_used = ~0) placed payloads at unknown
+    // offsets: nothing of that burst is handed out (the stack's own PushData runs)
+    pm.poisoned = used == ~0ull;
+    return 0;
+}
+
+// The message of the packet being replayed, if the window of tcbs[idx] takes it (RcvWindow::take).
 extern "C" int rxg_payload_take(rxg_ctx *c, int32_t idx, uint32_t seq, uint32_t length, rxg_payload_msg *msg)
 {
     if (!c) return fail(-EINVAL, "rxg_payload_take: ctx NULL");
-    const int64_t pos = c->attached.pos;
-    if (pos < 0 || (uint64_t)pos >= c->pm_n || length == 0 || length > 0xFFFFu) return 0;
-    if (c->pm_pending) {  // first take after the gather: fetch the burst's descriptors
-        if (int rc = set_device(c)) return rc;
-        HIP_OK(hipEventSynchronize(c->pm_ev));
-        if (c->pm_n > c->h_pm_cap) {
-            if (c->h_pm) HIP_OK(hipHostFree(c->h_pm));
-            c->h_pm = nullptr;
-            c->h_pm_cap = 0;
-            HIP_OK(hipHostMalloc((void **)&c->h_pm, (size_t)c->pm_n * sizeof(rxg_payload_msg), hipHostMallocDefault));
-            c->h_pm_cap = c->pm_n;
-        }
-        uint64_t used = 0;
-        HIP_OK(hipMemcpyAsync(c->h_pm, c->d_pm, (size_t)c->pm_n * sizeof(rxg_payload_msg), hipMemcpyDeviceToHost,
-                              c->stream));
-        if (c->pm_used)  // (a fused burst, rxg_rx_burst_payload_dev, has no look-back to time out)
-            HIP_OK(hipMemcpyAsync(&used, c->pm_used, sizeof used, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        c->pm_pending = false;
-        // a gather whose look-back timed out (arena_used = ~0) placed payloads at unknown
-        // offsets: nothing of that burst is handed out (the stack's own PushData runs)
-        c->pm_poisoned = used == ~0ull;
-    }
-    if (c->pm_poisoned) return 0;
-    const rxg_payload_msg &m = c->h_pm[pos];
-    if (!(m.flags & RXG_PM_GATHERED) || m.len != length) return 0;
-    if (idx < 0 || (size_t)idx >= c->rcv_state.size() || c->rcv_state[idx] != 1 || c->rcv_cur[idx] != seq)
-        return 0;
-    if (seq > (uint32_t)(seq + length)) return 0;  // the duplicate test drops it
-    if (seq == 0) return 0;  // GetData asserts CurrentSequenceNumber != 0 (:151): the stack's own code
-    c->rcv_cur[idx] = seq + length;
+    const int64_t pos = c->attached.position();
+    if (pos < 0 || (uint64_t)pos >= c->pm.n || length == 0 || length > 0xFFFFu) return 0;
+    if (c->pm.pending)  // first take after the gather
+        if (int rc = pm_fetch(c)) return rc;
+    if (c->pm.poisoned) return 0;
+    const rxg_payload_msg &m = c->pm.host[pos];
+    if (!c->rcv.take(idx, seq, length, m)) return 0;
     if (msg) *msg = m;
     return 1;
 }
 
-// ------------------------------------------------------------------ prebuilt resets ---
+// ---------------------------------------------------- what a replay hands out ---
+// (the rules: rxg::ReplayAttached, rxg_attached.h)
 extern "C" int rxg_reset_attach(rxg_ctx *c, void *resets_host, const uint32_t *idx_host, uint64_t nbuilt)
 {
     if (!c || (nbuilt && (!resets_host || !idx_host)))
         return fail(-EINVAL, "rxg_reset_attach: NULL argument");
-    ReplayAttached &a = c->attached;
-    a.rst_host = nbuilt ? (uint8_t *)resets_host : nullptr;
-    a.rst_idx = nbuilt ? idx_host : nullptr;
-    a.rst_n = nbuilt;
-    a.rst_cur = 0;
+    c->attached.attach_resets(resets_host, idx_host, nbuilt);
     return 0;
 }
 
-// idx_host ascends (resets come out in packet order) and the replay's position only grows:
-// one cursor, moved to the first entry at or after the packet being replayed.  An entry
-// passed over belongs to a frame that no longer wants its reset (re-classified to DISPATCH,
-// or dropped by the checksum verify).
 extern "C" int rxg_reset_take(rxg_ctx *c, uint16_t ip_id, void **frame_out)
 {
     if (!c || !frame_out) return fail(-EINVAL, "rxg_reset_take: NULL argument");
-    ReplayAttached &a = c->attached;
-    const int64_t pos = a.pos;
-    if (pos < 0 || !a.rst_host) return 0;
-    while (a.rst_cur < a.rst_n && (int64_t)a.rst_idx[a.rst_cur] < pos) ++a.rst_cur;
-    if (a.rst_cur >= a.rst_n || (int64_t)a.rst_idx[a.rst_cur] != pos) return 0;
-    uint8_t *f = a.rst_host + 64u * a.rst_cur;
-    if ((uint16_t)(f[18] | (f[19] << 8)) != ip_id) rxg_reset_set_id(f, ip_id);
+    uint8_t *f = c->attached.take_reset(ip_id);
+    if (!f) return 0;
     *frame_out = f;
     return 1;
 }
 
-// ------------------------------------------------------------------ parsed options ---
 extern "C" int rxg_rx_opts_attach(rxg_ctx *c, const rxg_rx_opt *opts_host, uint32_t n)
 {
     if (!c || (n && !opts_host)) return fail(-EINVAL, "rxg_rx_opts_attach: NULL argument");
-    c->attached.opt_host = n ? opts_host : nullptr;
-    c->attached.opt_n = n;
+    c->attached.attach_opts(opts_host, n);
     return 0;
 }
 
-// The record of the attached copy for the packet being replayed: options do not depend on the
-// mirror, so the record of a packet the replay re-classified is as good as any other's.
 extern "C" int rxg_rx_opt_current(rxg_ctx *c, const rxg_rx_opt **out)
 {
     if (!c || !out) return fail(-EINVAL, "rxg_rx_opt_current: NULL argument");
-    const ReplayAttached &a = c->attached;
-    const int64_t pos = a.pos;
-    if (pos < 0 || !a.opt_host || !a.opt_live || pos >= (int64_t)a.opt_n) return 0;
-    *out = a.opt_host + pos;
+    const rxg_rx_opt *o = c->attached.opt_current();
+    if (!o) return 0;
+    *out = o;
     return 1;
 }
 
-// ---------------------------------------------------------------- flow summaries ---
 extern "C" int rxg_flow_sums_attach(rxg_ctx *c, const rxg_flow_sum *sums_host, uint64_t m)
 {
     if (!c || (m && !sums_host)) return fail(-EINVAL, "rxg_flow_sums_attach: NULL argument");
-    for (uint64_t k = 1; k < m; ++k)
-        if (sums_host[k].tcb_idx <= sums_host[k - 1].tcb_idx)
-            return fail(-EINVAL, "rxg_flow_sums_attach: entry %llu is not above its predecessor's tcb_idx",
-                        (unsigned long long)k);
-    c->attached.fs_host = m ? sums_host : nullptr;
-    c->attached.fs_m = m;
+    uint64_t k = 0;
+    if (!c->attached.attach_flow_sums(sums_host, m, &k))
+        return fail(-EINVAL, "rxg_flow_sums_attach: entry %llu is not above its predecessor's tcb_idx",
+                    (unsigned long long)k);
     return 0;
 }
 
-// The packet being replayed, if its record is still the burst's (ReplayLog::as_burst: not
-// re-classified) and a DISPATCH to a flow of the attached list that covers its index.
 extern "C" int rxg_flow_sum_current(rxg_ctx *c, const rxg_flow_sum **out, uint32_t *pkt_idx)
 {
     if (!c || !out || !pkt_idx) return fail(-EINVAL, "rxg_flow_sum_current: NULL argument");
-    const ReplayAttached &a = c->attached;
-    const int64_t pos = a.pos;
-    if (pos < 0 || !a.fs_host || (uint64_t)pos >= c->replay.size()) return 0;
-    const rxg_rec16 &r = c->replay.record((size_t)pos);
-    if (!c->replay.as_burst((size_t)pos) || r.verdict != RXG_V_DISPATCH) return 0;
-    const rxg_flow_sum *lo = a.fs_host, *hi = a.fs_host + a.fs_m;
-    const rxg_flow_sum *s =
-        std::lower_bound(lo, hi, r.tcb_idx, [](const rxg_flow_sum &e, int32_t t) { return e.tcb_idx < t; });
-    if (s == hi || s->tcb_idx != r.tcb_idx || (uint64_t)pos < s->first_idx || (uint64_t)pos > s->last_idx) return 0;
+    const rxg_flow_sum *s = c->attached.flow_sum_current(c->replay, pkt_idx);
+    if (!s) return 0;
     *out = s;
-    *pkt_idx = (uint32_t)pos;
     return 1;
 }
 
-// ------------------------------------------------------------------- flow trains ---
 extern "C" int rxg_flow_trains_attach(rxg_ctx *c, const uint32_t *order_host, uint64_t nseg,
                                       const rxg_flow_train *trains_host, uint64_t ntrains)
 {
     if (!c || (nseg && !order_host) || (ntrains && !trains_host))
         return fail(-EINVAL, "rxg_flow_trains_attach: NULL argument");
-    uint64_t at = 0;
-    for (uint64_t k = 0; k < ntrains; ++k) {
-        const rxg_flow_train &t = trains_host[k];
-        if (t.first != at || t.nseg == 0 || (k && t.tcb_idx < trains_host[k - 1].tcb_idx))
-            return fail(-EINVAL, "rxg_flow_trains_attach: train %llu does not start where its predecessor ended "
-                                 "(first %u, nseg %u, expected first %llu)",
-                        (unsigned long long)k, t.first, t.nseg, (unsigned long long)at);
-        at += t.nseg;
-    }
-    ReplayAttached &a = c->attached;
-    a.ft_order = nseg ? order_host : nullptr;
-    a.ft_trains = ntrains ? trains_host : nullptr;
-    a.ft_nseg = nseg;
-    a.ft_ntrains = ntrains;
+    uint64_t k = 0, first = 0;
+    if (!c->attached.attach_flow_trains(order_host, nseg, trains_host, ntrains, &k, &first))
+        return fail(-EINVAL, "rxg_flow_trains_attach: train %llu does not start where its predecessor ended "
+                             "(first %u, nseg %u, expected first %llu)",
+                    (unsigned long long)k, trains_host[k].first, trains_host[k].nseg, (unsigned long long)first);
     return 0;
 }
 
-// The packet being replayed, if its record is still the burst's (ReplayLog::as_burst: not
-// re-classified) and a DISPATCH: the attached trains of its flow are found by tcb_idx, the packet
-// among the flow's segments (ascending packet indices), and its train by that position.
 extern "C" int rxg_flow_train_current(rxg_ctx *c, const rxg_flow_train **out, uint32_t *pos_out)
 {
     if (!c || !out || !pos_out) return fail(-EINVAL, "rxg_flow_train_current: NULL argument");
-    const ReplayAttached &a = c->attached;
-    const int64_t pos = a.pos;
-    if (pos < 0 || !a.ft_order || !a.ft_trains || (uint64_t)pos >= c->replay.size()) return 0;
-    const rxg_rec16 &r = c->replay.record((size_t)pos);
-    if (!c->replay.as_burst((size_t)pos) || r.verdict != RXG_V_DISPATCH) return 0;
-    const rxg_flow_train *lo = a.ft_trains, *hi = a.ft_trains + a.ft_ntrains;
-    const rxg_flow_train *tl =
-        std::lower_bound(lo, hi, r.tcb_idx, [](const rxg_flow_train &e, int32_t t) { return e.tcb_idx < t; });
-    const rxg_flow_train *th =
-        std::upper_bound(tl, hi, r.tcb_idx, [](int32_t t, const rxg_flow_train &e) { return t < e.tcb_idx; });
-    if (tl == th) return 0;
-    const uint64_t s0 = tl->first, s1 = std::min<uint64_t>((uint64_t)(th - 1)->first + (th - 1)->nseg, a.ft_nseg);
-    if (s0 >= s1) return 0;
-    const uint32_t *seg = std::lower_bound(a.ft_order + s0, a.ft_order + s1, (uint32_t)pos);
-    if (seg == a.ft_order + s1 || *seg != (uint32_t)pos) return 0;
-    const uint64_t q = (uint64_t)(seg - a.ft_order);
-    // the last train of the flow that starts at or before q
-    const rxg_flow_train *t =
-        std::upper_bound(tl, th, q, [](uint64_t v, const rxg_flow_train &e) { return v < e.first; }) - 1;
-    if ((uint64_t)t->first + t->nseg > a.ft_nseg) return 0;  // order was capped inside this train
+    const rxg_flow_train *t = c->attached.flow_train_current(c->replay, pos_out);
+    if (!t) return 0;
     *out = t;
-    *pos_out = (uint32_t)(q - t->first);
     return 1;
 }
 
-// ------------------------------------------------------------------ prebuilt ACKs ---
 extern "C" int rxg_acks_attach(rxg_ctx *c, const rxg_ack *acks_host, void *frames_host, uint32_t stride, uint64_t nacks)
 {
     if (!c || (nacks && (!acks_host || !frames_host || !stride)))
         return fail(-EINVAL, "rxg_acks_attach: NULL argument or stride 0");
-    for (uint64_t a = 1; a < nacks; ++a)
-        if (acks_host[a].tcb_idx <= acks_host[a - 1].tcb_idx)
-            return fail(-EINVAL, "rxg_acks_attach: entry %llu is not above its predecessor's tcb_idx",
-                        (unsigned long long)a);
-    ReplayAttached &a = c->attached;
-    a.acks_detach();
-    if (!nacks) return 0;
-    a.ak_acks = acks_host;
-    a.ak_frames = (uint8_t *)frames_host;
-    a.ak_stride = stride;
-    a.ak_n = nacks;
-    a.ak_phase = 1;
+    uint64_t a = 0;
+    if (!c->attached.attach_acks(acks_host, frames_host, stride, nacks, &a))
+        return fail(-EINVAL, "rxg_acks_attach: entry %llu is not above its predecessor's tcb_idx",
+                    (unsigned long long)a);
     return 0;
 }
 
-// The attached ACK of tcb_idx, if it still says what the stack's state says and nothing voids
-// it: no packet re-classified to or from the TCB, no write to its slot (the slot's tuple is among
-// the written ones, or the slot is gone), no whole-table change -- in the replay, or since it
-// returned (the writes not yet absorbed: rxg_ctx::touched, kept until the next burst).
+// (rxg_ctx::touched: the writes no replay has absorbed yet, kept until the next burst)
 extern "C" int rxg_ack_take(rxg_ctx *c, int32_t tcb_idx, uint32_t snd_nxt, uint32_t rcv_ack, void **frame_out)
 {
     if (!c || !frame_out) return fail(-EINVAL, "rxg_ack_take: NULL argument");
-    const ReplayAttached &a = c->attached;
-    if (a.ak_phase != 2u || a.ak_void_all) return 0;
-    const rxg_ack *lo = a.ak_acks, *hi = a.ak_acks + a.ak_n;
-    const rxg_ack *e = std::lower_bound(lo, hi, tcb_idx, [](const rxg_ack &x, int32_t t) { return x.tcb_idx < t; });
-    if (e == hi || e->tcb_idx != tcb_idx || e->seq != snd_nxt || e->ack != rcv_ack) return 0;
-    if (tcb_idx < 0 || tcb_idx >= c->mir.ntcb() || !c->mir.live[tcb_idx]) return 0;
-    TupleKey k;
-    if (!tcb_key(c->mir.tcb[tcb_idx], k)) return 0;
-    if (a.ak_void_tcb.count(tcb_idx) || a.ak_void_keys.count(k)) return 0;
-    if (c->touched.all || std::find(c->touched.keys.begin(), c->touched.keys.end(), k) != c->touched.keys.end()) return 0;
-    *frame_out = a.ak_frames + (size_t)(e - lo) * a.ak_stride;
+    uint8_t *f = c->attached.ack_take(tcb_idx, snd_nxt, rcv_ack, c->mir, c->touched);
+    if (!f) return 0;
+    *frame_out = f;
     return 1;
 }
 
@@ -388,36 +289,29 @@ static int reclassify(rxg_ctx *c, const std::vector<uint32_t> &sel, std::vector<
     return 0;
 }
 
-// One batch of table writes into the replay's log; with prebuilt ACKs handed out (ak_on), what
-// of it voids one (rxg_ack_take).
-static void absorb(rxg_ctx *c, bool ak_on, const WriteSet &w)
+// One batch of table writes into the replay's log, and to what the replay hands out.
+static void absorb(rxg_ctx *c, const WriteSet &w)
 {
-    if (ak_on) {
-        c->attached.ak_void_all |= w.all;
-        c->attached.ak_void_keys.insert(w.keys.begin(), w.keys.end());
-    }
+    c->attached.wrote(w);
     c->replay.absorb(w);
 }
 
 // The tracked writes since the last absorb; logged for the launch's later bursts, whose records
 // were computed before them too.
-static void absorb_touched(rxg_ctx *c, bool ak_on)
+static void absorb_touched(rxg_ctx *c)
 {
     c->launch_writes.add(c->touched);
-    absorb(c, ak_on, c->touched);
+    absorb(c, c->touched);
     c->touched.clear();
 }
 
-// Packet j's record becomes r: the counter corrections, the TCBs whose prebuilt ACK that voids.
-static void refix(rxg_ctx *c, bool ak_on, uint32_t j, const rxg_rec16 &r, int64_t *delta)
+// Packet j's record becomes r: the counter corrections, and what the replay hands out told.
+static void refix(rxg_ctx *c, uint32_t j, const rxg_rec16 &r, int64_t *delta)
 {
     const rxg_rec16 &old = c->replay.record(j);
     tcp_record_counters(old, -1, delta);
     tcp_record_counters(r, +1, delta);
-    if (ak_on) {
-        c->attached.ak_void_tcb.insert(old.tcb_idx);
-        c->attached.ak_void_tcb.insert(r.tcb_idx);
-    }
+    c->attached.refixed(old, r);
     c->replay.fixed(j, r);
 }
 
@@ -473,24 +367,13 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
 {
     if (!c) return fail(-EINVAL, "rxg_rx_replay: NULL argument");
     ReplayAttached &att = c->attached;
-    // on every way out: no packet is being replayed, and what was attached for this replay is no
-    // longer named
-    struct PosGuard {
+    // on every way out, a failed argument check included
+    struct Ending {
         ReplayAttached &a;
-        bool done = false;  // the replay ran to its end
-        ~PosGuard()
-        {
-            // prebuilt ACKs (rxg_acks_attach) are only handed out after a replay that saw the whole
-            // burst: one that fails, in its argument checks or later, ends the attachment
-            if (!done) a.acks_detach();
-            a.end_of_replay();
-        }
-    } pos_guard{att};
-    // the prebuilt ACKs (rxg_acks_attach) outlive one replay: an attachment that has had its
-    // replay ends here, a fresh one belongs to this burst (and ends with it if it fails: pos_guard)
-    if (att.ak_phase == 2u) att.acks_detach();
-    else if (att.ak_phase == 1u) att.ak_phase = 2u;
-    const bool ak_on = att.ak_phase == 2u;
+        bool ran_to_end = false;
+        ~Ending() { a.end_replay(ran_to_end); }
+    } ending{att};
+    att.begin_replay(n);
     if (!ops || (n && (!mbufs || !frames || !recs)))
         return fail(-EINVAL, "rxg_rx_replay: NULL argument");
     if (!rec_kind_ok(stride)) return fail(-EINVAL, "rxg_rx_replay: stride %u", stride);
@@ -501,12 +384,11 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
     // the re-classify launches and the counter correction run on this context's device
     // (a group replays several contexts from one thread, rxg_group.cpp)
     if (int rc = set_device(c)) return rc;
-    att.opt_live = att.opt_host && att.opt_n == n;  // (rxg_rx_opts_attach) the copy is this burst's
     ReplayLog &log = c->replay;
     log.begin(n, recs, stride);
     // writes the replays of this launch's earlier bursts made, then those since
-    if (c->replay_cursor > 0 && !c->launch_writes.empty()) absorb(c, ak_on, c->launch_writes);
-    if (!c->touched.empty()) absorb_touched(c, ak_on);
+    if (c->replay_cursor > 0 && !c->launch_writes.empty()) absorb(c, c->launch_writes);
+    if (!c->touched.empty()) absorb_touched(c);
 
     int64_t delta[RXG_NCOUNTERS] = {0};
     std::vector<uint32_t> sel;
@@ -516,20 +398,20 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
             const ReplayLog::Plan p = log.plan(i, frames, n, c->replay_on_device, sel);
             if (p == ReplayLog::kLaunch) {
                 if (int rc = reclassify(c, sel, fix)) return rc;
-                for (size_t k = 0; k < sel.size(); ++k) refix(c, ak_on, sel[k], fix[k], delta);
+                for (size_t k = 0; k < sel.size(); ++k) refix(c, sel[k], fix[k], delta);
             } else {
                 if (c->mir.need_rebuild)  // a reload / growth inside the replay: index first
                     if (int rc = tcb_push(c)) return rc;
                 rxg_rec16 r = log.record(i);
                 host_classify(c->mir, (const uint8_t *)frames[i], r);
-                refix(c, ak_on, i, r, delta);
+                refix(c, i, r, delta);
             }
             log.done(p, sel.size());
         }
-        att.pos = i;  // rxg_payload_take answers for this packet
+        att.at(i);  // what the handlers take is answered for this packet
         const uint64_t gen_before = c->gen;
         dispatch(c, ops, log.record(i), mbufs[i], (uint8_t *)frames[i]);
-        if (c->gen != gen_before) absorb_touched(c, ak_on);  // the handlers changed the table
+        if (c->gen != gen_before) absorb_touched(c);  // the handlers changed the table
     }
     // the launch's next burst is replayed next (a single burst can be replayed again)
     if (c->replay_cursor + 1 < c->last_bursts.size()) select_burst(c, c->replay_cursor + 1);
@@ -539,7 +421,7 @@ extern "C" int rxg_rx_replay(rxg_ctx *c, const rxg_handoff_ops *ops, void *const
         for (int k = 0; k < RXG_NCOUNTERS; ++k) c->pend_delta[k] += delta[k];
         c->pend = true;
     }
-    pos_guard.done = true;
+    ending.ran_to_end = true;
     return 0;
 }
 
